@@ -12,10 +12,17 @@ GPU, no data-path collective: "weak" scaling, each rank owns its own batch).
 value = (sum of object bytes encoded + decoded over all ranks) / (max over
 ranks of the timed K steps), in GiB/s.  roofline: algorithmic HBM bytes per
 launch of the dominant kernel (rs_apply_queue_kernel<8>) / its average duration,
-from HIP events recorded on the launch stream.  cpu_baseline: the oracle's
-faithful scalar C restatement of the reference's Go path, on a bounded sample.
+from HIP events recorded on the launch stream.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--objects B] [--object-mib S]
+A plain run sets up the batch, warms up, times the K steps and prints the
+line.  --full adds every other leg after the timed region (each with a switch
+of its own): the other BASELINE shapes, the fused byte path, the host paths,
+stream ceilings, the allocator probe and cpu_baseline -- the oracle's faithful
+scalar C restatement of the reference's Go path, on a bounded sample, which
+also pins every object of every timed batch to the oracle.  --dump-outputs DIR
+writes a seeded column sample of what the last timed step computed.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--objects B] [--object-mib S] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -70,6 +77,14 @@ def parse(argv=None):
                          "(tests the N-rank launch on a machine without GPUs)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (--cpu-baseline, --c5-leg, --bytes-path, "
+                         "--c5-bytes, --ceilings, --host-path, --pooled, --alloc-probe, --shape-legs: each on by "
+                         "default under --full, none of them runs without it)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/parity.npy (the encode "
+                         "launch's parity rows) and DIR/rebuilt.npy (the decode launch's erased rows): float64 "
+                         "[object][row][column] over a fixed seeded column sample of every object (dump_outputs)")
     ap.add_argument("--need", type=int, default=8)
     ap.add_argument("--total", type=int, default=12)
     ap.add_argument("--objects", type=int, default=128, help="objects per GPU (C3/C4: 128; weak scaling)")
@@ -135,6 +150,12 @@ def parse(argv=None):
                          ("global_objects", glob), ("erase", erase)):
             if "--" + key.replace("_", "-") not in given:  # explicit flags win over the preset
                 setattr(args, key, val)
+    if not args.full:
+        # A plain run does what `value` needs and nothing else: the legs wait for --full.
+        for key in ("cpu_baseline", "c5_leg", "bytes_path", "c5_bytes", "ceilings", "host_path", "pooled",
+                    "alloc_probe"):
+            setattr(args, key, 0)
+        args.shape_legs = ""
     return args
 
 
@@ -1155,13 +1176,13 @@ class SymbolBatch:
         return {"elapsed": elapsed, "enc_all": [e[0].elapsed_time(e[1]) for e in events],
                 "dec_all": [e[1].elapsed_time(e[2]) for e in events], "ok": ok}
 
-    def sample(self, seed: int) -> dict:
+    def sample(self, seed: int, ncols: int = ORACLE_COLS) -> dict:
         """column_sample of every object as the timed steps left it: the data
         rows (erased ones rebuilt by the last decode) and the parity rows of
         the last encode."""
-        smp = column_sample(self.buf.view(self.nobj, self.total, self.SS), self.L, seed)
+        smp = column_sample(self.buf.view(self.nobj, self.total, self.SS), self.L, seed, ncols)
         if self.decode_dst != "inplace":  # the rebuilt rows live in self.rec (same seed: same columns)
-            rec = column_sample(self.rec.view(self.nobj, len(self.erase), self.SS), self.L, seed)
+            rec = column_sample(self.rec.view(self.nobj, len(self.erase), self.SS), self.L, seed, ncols)
             smp["cols"][:, self.erase] = rec["cols"]
         smp.update(need=self.need, total=self.total, have=self.have)
         return smp
@@ -1175,6 +1196,35 @@ class SymbolBatch:
         del self.buf, self.rec
         torch.cuda.empty_cache()
         D.release_deferred()
+
+
+DUMP_SEED = 0xD0A7
+DUMP_BYTES = 60_000_000  # both arrays together stay under 64 MB
+
+
+def dump_outputs(path: str, sb: SymbolBatch, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step left in HBM, so that two builds
+    can be compared output for output (the inputs are seeded: the same
+    arguments give the same batch).  parity.npy: the rows need..total-1 the
+    encode launch wrote; rebuilt.npy: the erased rows the decode launch
+    rebuilt; both [object][row][column] in float64, which holds every 32-bit
+    symbol exactly.  The whole outputs are GiBs, so each array keeps
+    column_sample's columns of every object: a window of consecutive columns
+    at a per-object offset drawn from DUMP_SEED (ORACLE_COLS wide, narrower if
+    the batch has so many objects that the files would pass DUMP_BYTES) and
+    the last column.  Ranks of a multi-rank run write <name>.rank<r>.npy."""
+    import numpy as np
+
+    r, e = sb.total - sb.need, len(sb.erase)
+    ncols = max(1, min(ORACLE_COLS, DUMP_BYTES // (8 * max(1, sb.nobj) * (r + e)) - 1))
+    if sb.nobj:
+        cols = sb.sample(DUMP_SEED, ncols)["cols"]
+    else:  # a rank with no object of a partitioned batch
+        cols = np.zeros((0, sb.total, 0), dtype=np.uint32)
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"parity{suffix}.npy"), cols[:, sb.need:].astype(np.float64))
+    np.save(os.path.join(path, f"rebuilt{suffix}.npy"), cols[:, sb.erase].astype(np.float64))
 
 
 def symbol_traffic(args, need: int, total: int, L: int, nobj: int, kname: str) -> tuple:
@@ -1442,6 +1492,8 @@ def main():
     sb = SymbolBatch(args, dev, 0x5113E + 7919 * rank, need, total, S, nobj, erase, args.decode_dst)
     L, SS, lay, placement = sb.L, sb.SS, sb.lay, sb.placement
     res = sb.run(args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sb, rank, world)
     elapsed, enc_all, dec_all, ok = res["elapsed"], res["enc_all"], res["dec_all"], res["ok"]
     enc_ms = sum(enc_all) / args.steps
     dec_ms = sum(dec_all) / args.steps

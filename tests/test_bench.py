@@ -58,16 +58,16 @@ def test_gpus_n_launches_n_ranks_that_agree_on_the_partition():
 
 
 def test_dry_run_reports_the_c5_partition_at_every_n():
-    """Every `bench.py --gpus N` run carries BASELINE config 5 as a second leg:
+    """Every `bench.py --gpus N --full` run carries BASELINE config 5 as a second leg:
     64 x 1 GiB objects (10/14) partitioned over the N ranks -- 32 + 32 at
     N = 2, 8 x 8 at N = 8 -- beside the weak-scaling C3 leg."""
-    r = _bench(["--gpus", "2", "--dry-run"], SLIME_BENCH_DEVICE_COUNT="2")
+    r = _bench(["--gpus", "2", "--dry-run", "--full"], SLIME_BENCH_DEVICE_COUNT="2")
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
     c5 = line["c5_partitioned"]
     assert (c5["need"], c5["total"], c5["object_mib"], c5["objects"]) == (10, 14, 1024, 64)
     assert c5["partitions"] == [[0, 0, 0, 32], [1, 1, 32, 32]]
-    r = _bench(["--gpus", "8", "--dry-run"], SLIME_BENCH_DEVICE_COUNT="8")
+    r = _bench(["--gpus", "8", "--dry-run", "--full"], SLIME_BENCH_DEVICE_COUNT="8")
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["partitions"] == [[i, i, 128 * i, 128] for i in range(8)]
@@ -211,15 +211,15 @@ def test_matrix_core_labels_follow_the_library_rule():
 
 
 def test_dry_run_plans_the_c2_and_north_star_shape_legs():
-    """Every line carries BASELINE config 2 (4/6, 32 x 64 MiB) and the north
+    """Every --full line carries BASELINE config 2 (4/6, 32 x 64 MiB) and the north
     star's 64 MiB-shard shape (8/12, 64 x 512 MiB) per GPU beside C3+C4; a
     run whose main shape is one of them does not repeat it."""
-    r = _bench(["--gpus", "2", "--dry-run"], SLIME_BENCH_DEVICE_COUNT="2")
+    r = _bench(["--gpus", "2", "--dry-run", "--full"], SLIME_BENCH_DEVICE_COUNT="2")
     assert r.returncode == 0, r.stdout + r.stderr
     sh = json.loads(r.stdout.strip().splitlines()[-1])["shapes"]
     assert sh["c2"] == {"need": 4, "total": 6, "object_mib": 64, "objects_per_rank": 32, "scaling": "weak"}
     assert sh["ns64"] == {"need": 8, "total": 12, "object_mib": 512, "objects_per_rank": 64, "scaling": "weak"}
-    r = _bench(["--dry-run", "--preset", "c2"], SLIME_BENCH_DEVICE_COUNT="1")
+    r = _bench(["--dry-run", "--preset", "c2", "--full"], SLIME_BENCH_DEVICE_COUNT="1")
     sh = json.loads(r.stdout.strip().splitlines()[-1])["shapes"]
     assert set(sh) == {"ns64"}
     # ns64 re-lays the C3 batch's buffer: exactly the same number of words
@@ -230,12 +230,12 @@ def test_dry_run_plans_the_c2_and_north_star_shape_legs():
 
 
 def test_dry_run_plans_the_pooled_proxy_leg_at_every_n():
-    """At every N, rank 0 drives the host entry points as one proxy does (25
+    """At every N under --full, rank 0 drives the host entry points as one proxy does (25
     concurrent PUT + GET requests, SLIME_RS_ANY_DEVICE) over the GPUs of all
     N ranks: the device pool is restricted to exactly those GPUs."""
     for n in (1, 2, 8):
         args = ["--gpus", str(n), "--dry-run"] if n > 1 else ["--dry-run"]
-        r = _bench(args, SLIME_BENCH_DEVICE_COUNT=str(n))
+        r = _bench(args + ["--full"], SLIME_BENCH_DEVICE_COUNT=str(n))
         assert r.returncode == 0, r.stdout + r.stderr
         pooled = json.loads(r.stdout.strip().splitlines()[-1])["host_path.pooled"]
         assert pooled["driver_rank"] == 0 and pooled["threads"] == 25
@@ -343,3 +343,64 @@ def test_oracle_pin_counts_every_object_and_catches_one_bad_word():
     pin = bench.oracle_pin({"b": dict(smp, cols=wire, mapping=ms)})
     assert pin["b"]["verified_objects"] == nobj and pin["b"]["domain"] == "bytes"
     assert bench.oracle_pin({"b": dict(smp, cols=wire, mapping=ms ^ np.uint32(1))})["b"]["verified_objects"] == 0
+
+
+def test_plain_run_plans_no_leg_beyond_the_timed_steps():
+    """Without --full the run is the headline's timed steps alone: every other
+    leg is off, whatever its own switch says; --full turns them on, each still
+    under its own switch."""
+    bench = _load("bench.py", "bench_mod_full")
+    legs = ("cpu_baseline", "c5_leg", "bytes_path", "c5_bytes", "ceilings", "host_path", "pooled", "alloc_probe")
+    for argv in ([], ["--gpus", "1", "--steps", "3", "--warmup", "1"], ["--bytes-path", "1", "--shape-legs", "c2"]):
+        a = bench.parse(argv)
+        assert not a.full and not any(getattr(a, k) for k in legs) and a.shape_legs == ""
+    a = bench.parse(["--full"])
+    assert a.full and all(getattr(a, k) == 1 for k in legs) and a.shape_legs == "c2,ns64"
+    a = bench.parse(["--full", "--host-path", "0", "--shape-legs", "c2"])
+    assert a.host_path == 0 and a.pooled == 1 and a.shape_legs == "c2"
+    r = _bench(["--dry-run"], SLIME_BENCH_DEVICE_COUNT="1")
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["c5_partitioned"] is None and line["shapes"] == {} and line["object_bytes_paths"] == []
+    assert line["host_path.pooled"] is None
+
+
+@pytest.mark.parametrize("nobj,dst", [(5, "inplace"), (3, "separate"), (40000, "inplace")])
+def test_dump_outputs_writes_the_sampled_parity_and_rebuilt_rows(tmp_path, nobj, dst):
+    """--dump-outputs (dump_outputs over a batch laid out as SymbolBatch lays
+    it, here in host memory): parity.npy holds rows need..total-1 and
+    rebuilt.npy the erased rows (from the separate buffer under --decode-dst
+    separate), float64 equal to the 32-bit symbols, the same columns of both,
+    the last column included; the same call gives the same files, and a batch
+    of many objects narrows the window so both files stay under 64 MB."""
+    import numpy as np
+    import torch
+    bench = _load("bench.py", "bench_mod_dump")
+    need, total, erase = 4, 6, [0, 1]
+    L, SS = (9000, 9024) if nobj < 100 else (70, 128)
+    rng = np.random.default_rng(nobj)
+    buf = rng.integers(0, 2**32 - 5, size=(nobj, total, SS), dtype=np.uint32)
+    rec = rng.integers(0, 2**32 - 5, size=(nobj, len(erase), SS), dtype=np.uint32)
+    sb = object.__new__(bench.SymbolBatch)
+    sb.need, sb.total, sb.erase, sb.nobj, sb.L, sb.SS, sb.decode_dst = need, total, erase, nobj, L, SS, dst
+    sb.have = [i for i in range(total) if i not in erase][:need]
+    sb.buf = torch.from_numpy(buf.view(np.int32).reshape(-1))
+    sb.rec = sb.buf if dst == "inplace" else torch.from_numpy(rec.view(np.int32).reshape(-1))
+    bench.dump_outputs(str(tmp_path / "a"), sb, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), sb, 0, 1)
+    par, reb = np.load(tmp_path / "a" / "parity.npy"), np.load(tmp_path / "a" / "rebuilt.npy")
+    assert par.dtype == reb.dtype == np.float64
+    assert par.nbytes + reb.nbytes <= 64_000_000
+    w = par.shape[2] - 1
+    assert par.shape == (nobj, total - need, w + 1) and reb.shape == (nobj, len(erase), w + 1)
+    assert w == (4096 if nobj < 100 else min(L, 60_000_000 // (8 * nobj * 4) - 1))
+    assert np.array_equal(par, np.load(tmp_path / "b" / "parity.npy"))
+    assert np.array_equal(reb, np.load(tmp_path / "b" / "rebuilt.npy"))
+    src = buf[:, erase] if dst == "inplace" else rec
+    assert np.array_equal(par[:, :, w], buf[:, need:, L - 1]) and np.array_equal(reb[:, :, w], src[:, :, L - 1])
+    for o in range(min(nobj, 5)):  # the window: consecutive columns of the object, at one offset for all its rows
+        offs = [c for c in range(L - w + 1) if np.array_equal(par[o, 0, :w], buf[o, need, c:c + w])]
+        assert len(offs) == 1
+        c = offs[0]
+        assert np.array_equal(par[o, :, :w], buf[o, need:, c:c + w])
+        assert np.array_equal(reb[o, :, :w], src[o, :, c:c + w])

@@ -130,3 +130,37 @@ def test_device_legs_pin_every_object_to_the_oracle(alloc):
         {"s46": (5, 5), "s1014": (3, 3), "bytes": (6, 6)}
     assert pin["bytes"]["domain"] == "bytes"
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("dst", ["inplace", "separate"])
+def test_dump_outputs_holds_what_the_timed_steps_computed(tmp_path, dst):
+    """bench.py --dump-outputs on the GPU at a small odd shape: after
+    SymbolBatch.run, parity.npy is the oracle's parity of the batch's data rows
+    on the sampled columns (the last column among them) and rebuilt.npy equals
+    the erased data rows, in place or in the separate buffer; a second batch
+    from the same seed dumps the same arrays."""
+    import types
+
+    bench = _bench()
+    from oracle import oracle_c as OC
+    args = types.SimpleNamespace(allocator="vmm", shard_align=64)
+    need, total, erase, nobj = 4, 6, [1, 2], 3
+    dumps = []
+    for d in ("a", "b"):
+        sb = bench.SymbolBatch(args, 0, 0xD0D0, need, total, (1 << 20) + 12, nobj, erase, dst)
+        assert sb.run(2, 1)["ok"]
+        bench.dump_outputs(str(tmp_path / d), sb, 0, 1)
+        rows = sb.buf.view(nobj, total, sb.SS)[:, :, :sb.L].cpu().numpy().view(np.uint32)
+        sb.free()
+        dumps.append((np.load(tmp_path / d / "parity.npy"), np.load(tmp_path / d / "rebuilt.npy")))
+    (par, reb), (par2, reb2) = dumps
+    assert np.array_equal(par, par2) and np.array_equal(reb, reb2)
+    w = par.shape[2] - 1
+    assert par.dtype == reb.dtype == np.float64 and par.shape == reb.shape == (nobj, 2, w + 1) and w == 4096
+    for o in range(nobj):
+        ref = np.ascontiguousarray(rows[o].copy())
+        ref[need:] = 0
+        OC.encode_object(ref, need, total)
+        c = next(c for c in range(sb.L - w + 1) if np.array_equal(par[o, 0, :w], ref[need, c:c + w]))
+        assert np.array_equal(par[o, :, :w], ref[need:, c:c + w]) and np.array_equal(par[o, :, w], ref[need:, -1])
+        assert np.array_equal(reb[o, :, :w], ref[erase, c:c + w]) and np.array_equal(reb[o, :, w], ref[erase, -1])

@@ -27,7 +27,7 @@ run() {  # run <name> <limit-seconds> <command...>
 pmc() {
   local name=$1 counter=$2; shift 2
   run "$name" 300 timeout -s KILL 240 rocprofv3 --pmc "$counter" -d "$OUT/$name" -o pmc --output-format csv -- \
-    python3 bench.py "$@"
+    python3 bench.py --full "$@"
 }
 
 nproc > "$OUT/host.txt"; grep -m1 "model name" /proc/cpuinfo >> "$OUT/host.txt" || true
@@ -41,14 +41,14 @@ for step in "$@"; do
     tests_sched) run pytest_sched 400 python -u -m pytest tests/test_gpu_schedule.py -x -v --timeout 200 --timeout-method thread ;;
     tests_fuzz) run pytest_fuzz 400 python -u -m pytest tests/test_gpu_parity.py -x -v --timeout 300 --timeout-method thread -k "fuzz" ;;
     tests_bench) run pytest_bench 400 python -u -m pytest tests/test_gpu_bench.py -x -v --timeout 200 --timeout-method thread ;;
-    hostrep) for i in 1 2 3; do run hostrep_$i 400 python bench.py --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 --c5-leg 0 --shape-legs= --pooled 0 || exit 1; done ;;
+    hostrep) for i in 1 2 3; do run hostrep_$i 400 python bench.py --full --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 --c5-leg 0 --shape-legs= --pooled 0 || exit 1; done ;;
     proxysweep) run proxy_sweep 300 python tools/proxy_sweep.py --threads 1,4,8,16,25 --mib 64,1 --seconds 1.5 &&
                 run proxy_sweep_c0 300 env SLIME_RS_COPY_THREADS=0 python tools/proxy_sweep.py --threads 8,16,25 --mib 64,1 --seconds 1.5 &&
                 run proxy_sweep_c4 300 env SLIME_RS_COPY_THREADS=4 python tools/proxy_sweep.py --threads 8,16,25 --mib 64,1 --seconds 1.5 ;;
     # C2 gap: the same 4/6 kernel on 32 (C2), 64 and 128 objects of 64 MiB, and a rocprof trace of C2
-    c2size) for n in 32 64 128 32; do run c2size_$n 300 python bench.py --preset c2 --objects $n --bytes-path 0 --steps 20 --warmup 5 $NOLEGS || exit 1; done &&
+    c2size) for n in 32 64 128 32; do run c2size_$n 300 python bench.py --full --preset c2 --objects $n --bytes-path 0 --steps 20 --warmup 5 $NOLEGS || exit 1; done &&
             run c2prof 300 rocprofv3 --kernel-trace --stats -d "$OUT/c2prof" -o c2 --output-format csv -- \
-              python3 bench.py --preset c2 --bytes-path 0 --steps 20 --warmup 5 $NOLEGS ;;
+              python3 bench.py --full --preset c2 --bytes-path 0 --steps 20 --warmup 5 $NOLEGS ;;
     proxyq) run proxy_q8 300 env GPU_MAX_HW_QUEUES=8 python tools/proxy_sweep.py --threads 8,16,25 --mib 64,1 --seconds 1.5 &&
             run proxy_q16 300 env GPU_MAX_HW_QUEUES=16 python tools/proxy_sweep.py --threads 8,16,25 --mib 64,1 --seconds 1.5 ;;
     proxysched) for sc in auto yield blocking spin; do
@@ -64,7 +64,7 @@ for step in "$@"; do
                 if [ "$v" = new ]; then cp /tmp/ab_new.so slime_amd/lib/libslime_rs.so; else cp ab/$v/libslime_rs.so slime_amd/lib/libslime_rs.so; fi
                 for shp in "80 100 $E16,16,17,18,19" "64 80 $E16" "72 90 $E16,16,17"; do
                   set -- $shp
-                  run wab_$1_$2_${v}_$rep 300 python bench.py --need $1 --total $2 --objects 32 --erase $3 $WB || exit 1
+                  run wab_$1_$2_${v}_$rep 300 python bench.py --full --need $1 --total $2 --objects 32 --erase $3 $WB || exit 1
                 done
               done
             done
@@ -73,7 +73,7 @@ for step in "$@"; do
     wshape) for shp in "64 80" "64 84" "80 96" "80 100" "72 88" "72 90" "48 64" "48 68"; do
               set -- $shp
               E=$(python -c "print(','.join(map(str,range($2-$1))))")
-              run wsh_$1_$2 300 python bench.py --need $1 --total $2 --objects 32 --erase $E --bytes-path 0 --steps 5 --warmup 2 $NOLEGS || exit 1
+              run wsh_$1_$2 300 python bench.py --full --need $1 --total $2 --objects 32 --erase $E --bytes-path 0 --steps 5 --warmup 2 $NOLEGS || exit 1
             done ;;
     wpmc80) E20=0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19
             pmc wpmc80_fetch FETCH_SIZE --need 80 --total 100 --objects 32 --erase $E20 --steps 3 --warmup 1 $NOLEGS &&
@@ -83,7 +83,7 @@ for step in "$@"; do
     wshape2) for shp in "64 96" "80 96" "48 80" "64 80" "32 64" "80 100"; do
               set -- $shp
               E=$(python -c "print(','.join(map(str,range($2-$1))))")
-              run wsh2_$1_$2 300 python bench.py --need $1 --total $2 --objects 32 --erase $E --bytes-path 0 --steps 5 --warmup 2 $NOLEGS || exit 1
+              run wsh2_$1_$2 300 python bench.py --full --need $1 --total $2 --objects 32 --erase $E --bytes-path 0 --steps 5 --warmup 2 $NOLEGS || exit 1
             done ;;
     # k > 80: this tree vs ab/* on 96/100, 90/100 (six K steps) and 100/116 (seven)
     wideab2) WB="--steps 5 --warmup 2 $NOLEGS"
@@ -94,7 +94,7 @@ for step in "$@"; do
                  for shp in "96 100" "90 100" "100 116"; do
                    set -- $shp
                    E=$(python -c "print(','.join(map(str,range($2-$1))))")
-                   run wab_$1_$2_${v}_$rep 300 python bench.py --need $1 --total $2 --objects 32 --erase $E $WB || exit 1
+                   run wab_$1_$2_${v}_$rep 300 python bench.py --full --need $1 --total $2 --objects 32 --erase $E $WB || exit 1
                  done
                done
              done
@@ -110,7 +110,7 @@ for step in "$@"; do
             E=$(python -c "print(','.join(map(str,range(min(4, $2-$1)))))")
             for om in "256 32" "32 256" "8 1024"; do
               set -- $1 $2 $om
-              run wtlb_$1_$2_$3 300 python bench.py --need $1 --total $2 --object-mib $3 --objects $4 --erase $E --bytes-path 0 --steps 5 --warmup 2 $NOLEGS || exit 1
+              run wtlb_$1_$2_$3 300 python bench.py --full --need $1 --total $2 --object-mib $3 --objects $4 --erase $E --bytes-path 0 --steps 5 --warmup 2 $NOLEGS || exit 1
             done
           done ;;
     wilv) for rep in 1 2; do
@@ -153,19 +153,19 @@ for step in "$@"; do
                done ;;
     wprof80) E20=0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19
              run wprof80 300 rocprofv3 --kernel-trace --stats -d "$OUT/wprof80" -o bench --output-format csv -- \
-               python3 bench.py --need 80 --total 100 --objects 32 --erase $E20 --steps 3 --warmup 1 $NOLEGS ;;
+               python3 bench.py --full --need 80 --total 100 --objects 32 --erase $E20 --steps 3 --warmup 1 $NOLEGS ;;
     tests_full) run pytest_full 600 python -u -m pytest tests/test_gpu_fullsize.py -x -v --timeout 300 --timeout-method thread ;;
-    bench20) run bench20 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
-    benchq) run benchq 400 python bench.py --steps 5 --warmup 1 --cpu-baseline 0 --host-path 0 --alloc-probe 0 --bytes-path 0 ;;
-    hostonly) run hostonly 400 python bench.py --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 --c5-leg 0 --shape-legs= ;;
-    rehearse2) run rehearse2 400 env SLIME_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --objects 32 --steps 5 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 &&
+    bench20) run bench20 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
+    benchq) run benchq 400 python bench.py --full --steps 5 --warmup 1 --cpu-baseline 0 --host-path 0 --alloc-probe 0 --bytes-path 0 ;;
+    hostonly) run hostonly 400 python bench.py --full --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 --c5-leg 0 --shape-legs= ;;
+    rehearse2) run rehearse2 400 env SLIME_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --objects 32 --steps 5 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 &&
                run rehearse2_torchrun 400 env SLIME_BENCH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --objects 32 --steps 5 --warmup 1 --bytes-path 0 \
+                 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --objects 32 --steps 5 --warmup 1 --bytes-path 0 \
                  --cpu-baseline 0 --alloc-probe 0 ;;
     # the driver's command under the profiler, without the pooled leg (rocprofv3 segfaulted
     # inside the runtime under its 25 concurrent host threads, profiles/r05/s4_pmc_c2/c2prof.log)
     profdrv) run profdrv 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- \
-            python3 bench.py --gpus 1 --steps 20 --warmup 5 --pooled 0 ;;
+            python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --pooled 0 ;;
     # PMC traffic passes per BASELINE shape (symbol path), each its own run
     pmc_c3) pmc pmc_c3_fetch FETCH_SIZE --steps 3 --warmup 1 $NOLEGS --bytes-path 0 &&
             pmc pmc_c3_write WRITE_SIZE --steps 3 --warmup 1 $NOLEGS --bytes-path 0 ;;

@@ -27,7 +27,7 @@ run() {  # run <name> <limit-seconds> <command...>
 pmc() {
   local name=$1 counter=$2; shift 2
   run "$name" 300 timeout -s KILL 240 rocprofv3 --pmc "$counter" -d "$OUT/$name" -o pmc --output-format csv -- \
-    python3 bench.py "$@"
+    python3 bench.py --full "$@"
 }
 
 nproc > "$OUT/host.txt"; grep -m1 "model name" /proc/cpuinfo >> "$OUT/host.txt" || true
@@ -40,16 +40,16 @@ for step in "$@"; do
     tests_mfma) run pytest_mfma 600 python -u -m pytest tests/test_gpu_mfma.py -x -q --timeout 300 --timeout-method thread ;;
     tests_bench) run pytest_bench 400 python -u -m pytest tests/test_gpu_bench.py -x -v --timeout 200 --timeout-method thread ;;
     tests_full) run pytest_full 600 python -u -m pytest tests/test_gpu_fullsize.py -x -v --timeout 300 --timeout-method thread ;;
-    bench20) run bench20 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    bench20) run bench20 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
     # the driver's command under the profiler WITH the pooled leg
     profpool) run profpool 700 rocprofv3 --kernel-trace --stats -d "$OUT/profpool" -o bench --output-format csv -- \
-            python3 bench.py --gpus 1 --steps 20 --warmup 5 &&
+            python3 bench.py --full --gpus 1 --steps 20 --warmup 5 &&
             python tools/prof_summary.py "$OUT/profpool" > "$OUT/profpool_summary.json" &&
             rm -f "$OUT/profpool/bench_kernel_trace.csv" ;;
     # only the pooled leg under the profiler (short), to reproduce the r05 fault quickly
     profpoolonly) run profpoolonly 400 rocprofv3 --kernel-trace --stats -d "$OUT/profpoolonly" -o pool --output-format csv -- \
-            python3 bench.py --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --host-path 0 --alloc-probe 0 --c5-leg 0 --shape-legs= ;;
-    hostonly) run hostonly 400 python bench.py --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 --c5-leg 0 --shape-legs= ;;
+            python3 bench.py --full --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --host-path 0 --alloc-probe 0 --c5-leg 0 --shape-legs= ;;
+    hostonly) run hostonly 400 python bench.py --full --objects 8 --steps 2 --warmup 1 --bytes-path 0 --cpu-baseline 0 --alloc-probe 0 --c5-leg 0 --shape-legs= ;;
     pmc_c3) pmc pmc_c3_fetch FETCH_SIZE --steps 3 --warmup 1 $NOLEGS --bytes-path 0 &&
             pmc pmc_c3_write WRITE_SIZE --steps 3 --warmup 1 $NOLEGS --bytes-path 0 ;;
     pmc_c2) pmc pmc_c2_fetch FETCH_SIZE --preset c2 --steps 3 --warmup 1 $NOLEGS --bytes-path 0 &&
@@ -118,11 +118,11 @@ for step in "$@"; do
       done ;;
     # the driver's command under the profiler, without the pooled leg (the profiler's own fault, s1_segv)
     profdrv) run profdrv 700 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- \
-            python3 bench.py --gpus 1 --steps 20 --warmup 5 --pooled 0 &&
+            python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --pooled 0 &&
             python tools/prof_summary.py "$OUT/prof" > "$OUT/prof_summary.json" ;;
-    rehearse2) run rehearse2 500 env SLIME_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --objects 32 --steps 5 --warmup 1 --cpu-baseline 0 --alloc-probe 0 &&
+    rehearse2) run rehearse2 500 env SLIME_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --objects 32 --steps 5 --warmup 1 --cpu-baseline 0 --alloc-probe 0 &&
                run rehearse2_torchrun 500 env SLIME_BENCH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --objects 32 --steps 5 --warmup 1 --cpu-baseline 0 --alloc-probe 0 ;;
+                 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --objects 32 --steps 5 --warmup 1 --cpu-baseline 0 --alloc-probe 0 ;;
     # what one fused byte encode call enqueues, and the gaps between (C5 and C3 shapes)
     etl) run etl_c5_plain 300 python tools/encode_timeline.py run &&
          run etl_c5 300 rocprofv3 --kernel-trace -d "$OUT/etl_c5" -o etl --output-format csv -- python3 tools/encode_timeline.py run &&
@@ -136,7 +136,7 @@ for step in "$@"; do
       run c5s_32 300 $C --nobj 32 --reps 6 --geometry 0:0,1:0,4:0,2:512 &&
       run c5s_8b 300 $C --nobj 8 --reps 10 --geometry 0:0,4:0,2:0 ;;
     # four ranks on one GPU: the N = 4 code paths (shape legs limited to C2 so four ranks fit in one HBM)
-    rehearse4) run rehearse4 500 env SLIME_BENCH_SHARE_GPU=1 python bench.py --gpus 4 --objects 32 --steps 3 --warmup 1 --cpu-baseline 0 --alloc-probe 0 --shape-legs=c2 ;;
+    rehearse4) run rehearse4 500 env SLIME_BENCH_SHARE_GPU=1 python bench.py --full --gpus 4 --objects 32 --steps 3 --warmup 1 --cpu-baseline 0 --alloc-probe 0 --shape-legs=c2 ;;
     # slime's default redundancy 3/5 (multi_config.go:139,152) as a device batch: the narrow-code spread rule
     spread35) C="python tools/c2_stamps.py --need 3 --total 5 --mib 64"
       run ss35_32 300 $C --nobj 32 --reps 16 --geometry 0:0,2:0,4:0,16:0 &&
@@ -149,7 +149,7 @@ for step in "$@"; do
     # the profiler's fault against the number of concurrent callers (first crash ends the session)
     profthreads) for t in ${PROF_THREADS:-2 4 8 16}; do
         run profpool_t$t 400 rocprofv3 --kernel-trace --stats -d "$OUT/profpool_t$t" -o pool --output-format csv -- \
-          python3 bench.py --objects 8 --steps 2 --warmup 1 --bytes-path 0 --c5-bytes 0 --cpu-baseline 0 --host-path 0 \
+          python3 bench.py --full --objects 8 --steps 2 --warmup 1 --bytes-path 0 --c5-bytes 0 --cpu-baseline 0 --host-path 0 \
           --alloc-probe 0 --c5-leg 0 --shape-legs= --pool-threads $t || exit 1
         rm -f "$OUT/profpool_t$t/pool_kernel_trace.csv"  # tens of MB a run; the stats CSV stays
       done ;;

@@ -42,12 +42,12 @@ nproc > "$OUT/host.txt"; grep -m1 "model name" /proc/cpuinfo >> "$OUT/host.txt" 
 has tests && run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 has smoke && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 has micro && run micro 600 python tools/microbench.py
-has bench && run bench 600 python bench.py
+has bench && run bench 600 python bench.py --full
 if has bench3; then
-  for i in 1 2 3; do run bench_rep$i 300 python bench.py --cpu-baseline 0; done
+  for i in 1 2 3; do run bench_rep$i 300 python bench.py --full --cpu-baseline 0; done
 fi
 has prof && run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- \
-  python3 bench.py --steps 5 --warmup 1 --cpu-baseline 0
+  python3 bench.py --full --steps 5 --warmup 1 --cpu-baseline 0
 has ubench && run ubench 600 python tools/ubench.py
 has variants && run variants 600 python tools/apply_variants.py
 if has placement; then
@@ -80,7 +80,7 @@ if has variants2; then
 fi
 if has grid; then
   for g in 1024 4096 8192; do
-    run bench_grid$g 300 env SLIME_RS_GRID_TARGET=$g python bench.py --steps 5 --cpu-baseline 0
+    run bench_grid$g 300 env SLIME_RS_GRID_TARGET=$g python bench.py --full --steps 5 --cpu-baseline 0
   done
 fi
 has placeprobe && run placeprobe 600 python tools/placement_probe.py
@@ -101,16 +101,16 @@ if has gridk; then  # block budget per k (SLIME_RS_GRID_TARGET), device-resident
   for kn in "8 12 256 128 0,1,2,3" "10 14 1024 16 0,1,2,3" "12 16 1024 16 0,1,2,3" "16 20 1024 16 0,1,2,3" "4 6 64 32 0,1"; do
     set -- $kn
     for g in 256 512 1024; do
-      run gridk_${1}_${2}_g$g 300 env SLIME_RS_GRID_TARGET=$g python bench.py --need $1 --total $2 --object-mib $3 \
+      run gridk_${1}_${2}_g$g 300 env SLIME_RS_GRID_TARGET=$g python bench.py --full --need $1 --total $2 --object-mib $3 \
         --objects $4 --erase $5 --steps 5 --warmup 1 --cpu-baseline 0 --bytes-path 0 --host-path 0
     done
   done
 fi
-if has shapes; then  # BASELINE shapes through bench.py (device-resident, encode + repair)
-  run shape_c3_64mib_shards 300 python bench.py --object-mib 512 --objects 64 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run shape_c2 300 python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run shape_c5_all64 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run shape_c4_mixed 300 python bench.py --erase 0,3,8,11 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+if has shapes; then  # BASELINE shapes through bench.py --full (device-resident, encode + repair)
+  run shape_c3_64mib_shards 300 python bench.py --full --object-mib 512 --objects 64 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run shape_c2 300 python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run shape_c5_all64 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run shape_c4_mixed 300 python bench.py --full --erase 0,3,8,11 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
 fi
 if has segs; then  # column segments per object (more independent stripe streams for small batches)
   run segs_c2 300 python tools/apply_variants.py --need 4 --total 6 --mib 64 --nobj 32 --variants 8 --blocks 512,1024 --nseg 1,2,4,8
@@ -121,11 +121,11 @@ if has segs; then  # column segments per object (more independent stripe streams
 fi
 if has shapes2; then  # product defaults vs forced segment counts on the small-batch shapes
   for sg in 0 1 4 16; do
-    run sh2_c2_s$sg 300 env SLIME_RS_SEGMENTS=$sg python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-    run sh2_c5_s$sg 300 env SLIME_RS_SEGMENTS=$sg python bench.py --need 10 --total 14 --object-mib 1024 --objects 16 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+    run sh2_c2_s$sg 300 env SLIME_RS_SEGMENTS=$sg python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+    run sh2_c5_s$sg 300 env SLIME_RS_SEGMENTS=$sg python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 16 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
   done
-  run sh2_c3 300 python bench.py --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run sh2_c5_all64 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run sh2_c3 300 python bench.py --full --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run sh2_c5_all64 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
 fi
 if has slowsegs; then  # on a slow allocation (if the box has one): do more independent streams help?
   run slowsegs_enc 400 python tools/apply_variants.py --hunt slow --variants 8,11 --blocks 512,1024 --nseg 1,2,4,8,16
@@ -137,24 +137,24 @@ if has offsets; then  # batch base offset inside one allocation; once plain, onc
   run offsets_prof 300 rocprofv3 --kernel-trace -d "$OUT/offsets_prof" -o run --output-format csv -- python3 tools/offset_probe.py
 fi
 if has widek; then  # k > 16: the generic one-column kernel
-  run widek_16_20 300 python bench.py --need 16 --total 20 --object-mib 256 --objects 32 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run widek_20_24 300 python bench.py --need 20 --total 24 --object-mib 256 --objects 32 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run widek_32_40 300 python bench.py --need 32 --total 40 --object-mib 256 --objects 32 --erase 0,1,2,3,4,5,6,7 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run widek_64_80 300 python bench.py --need 64 --total 80 --object-mib 256 --objects 16 --erase 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run widek_16_20 300 python bench.py --full --need 16 --total 20 --object-mib 256 --objects 32 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run widek_20_24 300 python bench.py --full --need 20 --total 24 --object-mib 256 --objects 32 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run widek_32_40 300 python bench.py --full --need 32 --total 40 --object-mib 256 --objects 32 --erase 0,1,2,3,4,5,6,7 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run widek_64_80 300 python bench.py --full --need 64 --total 80 --object-mib 256 --objects 16 --erase 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
 fi
 if has ranks2; then  # the N > 1 path end to end: 2 ranks sharing this box's one GPU
   run ranks2 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --objects 64
+    --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --objects 64
 fi
 if has widebytes; then  # fused byte path at need > 16
-  run widebytes_20_24 300 python bench.py --need 20 --total 24 --object-mib 256 --objects 32 --steps 3 --cpu-baseline 0 --host-path 0
-  run widebytes_40_56 300 python bench.py --need 40 --total 56 --object-mib 256 --objects 16 --erase 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15 --steps 3 --cpu-baseline 0 --host-path 0
+  run widebytes_20_24 300 python bench.py --full --need 20 --total 24 --object-mib 256 --objects 32 --steps 3 --cpu-baseline 0 --host-path 0
+  run widebytes_40_56 300 python bench.py --full --need 40 --total 56 --object-mib 256 --objects 16 --erase 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15 --steps 3 --cpu-baseline 0 --host-path 0
 fi
 if has sizes; then  # object size vs k: is 10/14 slower because of k or because of 1 GiB objects?
-  run sizes_10_14_256m 300 python bench.py --need 10 --total 14 --object-mib 256 --objects 128 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run sizes_8_12_1g 300 python bench.py --need 8 --total 12 --object-mib 1024 --objects 32 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run sizes_10_14_1g 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 32 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
-  run sizes_8_12_256m 300 python bench.py --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run sizes_10_14_256m 300 python bench.py --full --need 10 --total 14 --object-mib 256 --objects 128 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run sizes_8_12_1g 300 python bench.py --full --need 8 --total 12 --object-mib 1024 --objects 32 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run sizes_10_14_1g 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 32 --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
+  run sizes_8_12_256m 300 python bench.py --full --steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0
 fi
 if has clocks; then  # box state under sustained load: which clocks/limits differ on slow-placement boxes?
   ( timeout -k 5 40 python tools/sustained.py --seconds 12 --idle 1 > "$OUT/clocks_load.log" 2>&1 ) &
@@ -172,12 +172,12 @@ if has slowsweep; then  # kernel knobs on whatever box this is (the log names it
   run sweep_dec 400 python tools/apply_variants.py --decode 1 --separate 0 --variants 8,2,6,11 --blocks 256,512,1024,2048 --nseg 1,4,16
 fi
 if has bytesshapes; then  # fused byte path on small and large batches
-  run bshape_c2 300 python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 --cpu-baseline 0 --host-path 0
-  run bshape_c5 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 16 --steps 3 --cpu-baseline 0 --host-path 0
+  run bshape_c2 300 python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 --cpu-baseline 0 --host-path 0
+  run bshape_c5 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 16 --steps 3 --cpu-baseline 0 --host-path 0
 fi
 if has c5segs; then  # C5 (10/14, 64 x 1 GiB) with forced segment counts
   for sg in 0 2 8 16; do
-    run c5segs_s$sg 300 env SLIME_RS_SEGMENTS=$sg python bench.py --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
+    run c5segs_s$sg 300 env SLIME_RS_SEGMENTS=$sg python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0
   done
 fi
 if has k10; then  # why is 10/14 slower than 8/12?  unroll x blocks x segments at C5 shape (64 x 1 GiB -> 32 here)
@@ -233,9 +233,9 @@ if has pmcplace; then  # counters that may separate the fast/slow placement mode
 fi
 if has pmc; then
   run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o bench --output-format csv -- \
-    python3 bench.py --steps 2 --warmup 1 --cpu-baseline 0
+    python3 bench.py --full --steps 2 --warmup 1 --cpu-baseline 0
   run pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o bench --output-format csv -- \
-    python3 bench.py --steps 2 --warmup 1 --cpu-baseline 0
+    python3 bench.py --full --steps 2 --warmup 1 --cpu-baseline 0
 fi
 if has pipe; then  # software-pipelined apply kernel (variants 13-15) against the product forms
   V=8,10,6,13,14,15
@@ -256,18 +256,18 @@ fi
 if has pipeab; then  # product dispatch with and without the pipelined kernel, BASELINE shapes, same box
   B="--steps 5 --cpu-baseline 0 --bytes-path 0 --host-path 0"
   for pp in 1 0; do
-    run ab_c3_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py $B
-    run ab_c2_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 $B
-    run ab_c5_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --need 10 --total 14 --object-mib 1024 --objects 32 $B
-    run ab_64mib_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --object-mib 512 --objects 64 $B
+    run ab_c3_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full $B
+    run ab_c2_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 $B
+    run ab_c5_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 32 $B
+    run ab_64mib_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --object-mib 512 --objects 64 $B
   done
 fi
-if has bytesab; then  # byte kernels with and without the pipeline (both legs of bench.py switch)
+if has bytesab; then  # byte kernels with and without the pipeline (both legs of bench.py --full switch)
   B="--steps 5 --cpu-baseline 0 --host-path 0"
   for pp in 1 0; do
-    run bab_c3_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py $B
-    run bab_c2_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 $B
-    run bab_c5_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --need 10 --total 14 --object-mib 1024 --objects 16 $B
+    run bab_c3_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full $B
+    run bab_c2_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 $B
+    run bab_c5_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 16 $B
   done
 fi
 if has c5geo; then  # 10/14 geometry with the pipelined kernel: segments x segments-in-flight x blocks
@@ -278,17 +278,17 @@ if has wideab; then  # k > 16: pipelined wide kernel vs the chunked one, and its
   B="--object-mib 256 --steps 3 --cpu-baseline 0 --bytes-path 0 --host-path 0"
   for cfg in "20 24 32 0,1,2,3" "32 40 32 0,1,2,3,4,5,6,7" "64 80 16 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15"; do
     set -- $cfg
-    run wab_$1_$2_p1 300 env SLIME_RS_PIPE=1 python bench.py --need $1 --total $2 --objects $3 --erase $4 $B
-    run wab_$1_$2_p0 300 env SLIME_RS_PIPE=0 python bench.py --need $1 --total $2 --objects $3 --erase $4 $B
-    run wab_$1_$2_p1_g256 300 env SLIME_RS_PIPE=1 SLIME_RS_GRID_TARGET=256 python bench.py --need $1 --total $2 --objects $3 --erase $4 $B
-    run wab_$1_$2_p1_g1024 300 env SLIME_RS_PIPE=1 SLIME_RS_GRID_TARGET=1024 python bench.py --need $1 --total $2 --objects $3 --erase $4 $B
+    run wab_$1_$2_p1 300 env SLIME_RS_PIPE=1 python bench.py --full --need $1 --total $2 --objects $3 --erase $4 $B
+    run wab_$1_$2_p0 300 env SLIME_RS_PIPE=0 python bench.py --full --need $1 --total $2 --objects $3 --erase $4 $B
+    run wab_$1_$2_p1_g256 300 env SLIME_RS_PIPE=1 SLIME_RS_GRID_TARGET=256 python bench.py --full --need $1 --total $2 --objects $3 --erase $4 $B
+    run wab_$1_$2_p1_g1024 300 env SLIME_RS_PIPE=1 SLIME_RS_GRID_TARGET=1024 python bench.py --full --need $1 --total $2 --objects $3 --erase $4 $B
   done
 fi
 if has widebytesab; then  # need > 16 byte path: pipelined wide decode vs the chunked one
   B="--object-mib 256 --steps 3 --cpu-baseline 0 --host-path 0"
   for pp in 1 0; do
-    run wbab_20_24_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --need 20 --total 24 --objects 32 $B
-    run wbab_40_56_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --need 40 --total 56 --objects 16 --erase 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15 $B
+    run wbab_20_24_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --need 20 --total 24 --objects 32 $B
+    run wbab_40_56_p$pp 300 env SLIME_RS_PIPE=$pp python bench.py --full --need 40 --total 56 --objects 16 --erase 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15 $B
   done
 fi
 if has mathcost; then  # pipelined kernel with XOR stand-in math: is the field math on the critical path?
@@ -315,22 +315,22 @@ if has segalign; then  # column segments rounded to whole 1 KiB: 10/14 (odd spli
   run sa_c5dec 300 python tools/apply_variants.py --need 10 --total 14 --mib 1024 --nobj 32 --decode 1 --separate 0 --variants 15 --blocks 256 --nseg 8 --pad 0,38
   run sa_c3 300 python tools/apply_variants.py --variants 15 --blocks 256 --nseg 2
   B="--cpu-baseline 0 --host-path 0"
-  run sa_bench_c5_64 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 $B
-  run sa_bench_c5_32 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 32 --steps 5 $B
-  run sa_bench_c10_256 300 python bench.py --need 10 --total 14 --object-mib 256 --objects 128 --steps 5 $B
-  run sa_bench_c2 300 python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 $B
-  run sa_bench_c3 300 python bench.py --steps 5 $B
+  run sa_bench_c5_64 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 $B
+  run sa_bench_c5_32 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 32 --steps 5 $B
+  run sa_bench_c10_256 300 python bench.py --full --need 10 --total 14 --object-mib 256 --objects 128 --steps 5 $B
+  run sa_bench_c2 300 python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 $B
+  run sa_bench_c3 300 python bench.py --full --steps 5 $B
 fi
 if has shardalign; then  # bench with line-aligned shard strides (default) vs packed (--shard-align 1)
   B="--cpu-baseline 0 --host-path 0 --bytes-path 0"
   for al in 64 1; do
-    run al${al}_c5_64 300 python bench.py --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --shard-align $al $B
-    run al${al}_c10_256 300 python bench.py --need 10 --total 14 --object-mib 256 --objects 128 --steps 5 --shard-align $al $B
+    run al${al}_c5_64 300 python bench.py --full --need 10 --total 14 --object-mib 1024 --objects 64 --steps 3 --shard-align $al $B
+    run al${al}_c10_256 300 python bench.py --full --need 10 --total 14 --object-mib 256 --objects 128 --steps 5 --shard-align $al $B
   done
-  run al64_c3 300 python bench.py --steps 5 $B
-  run al64_c2 300 python bench.py --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 $B
-  run al64_c4mixed 300 python bench.py --erase 0,3,8,11 --steps 5 $B
-  run al64_c3_sep 300 python bench.py --decode-dst separate --steps 5 $B
+  run al64_c3 300 python bench.py --full --steps 5 $B
+  run al64_c2 300 python bench.py --full --need 4 --total 6 --object-mib 64 --objects 32 --erase 0,1 --steps 5 $B
+  run al64_c4mixed 300 python bench.py --full --erase 0,3,8,11 --steps 5 $B
+  run al64_c3_sep 300 python bench.py --full --decode-dst separate --steps 5 $B
 fi
 if has pipe4; then  # 4 KiB tiles per wave per stream (pipe U4) against the product U3, C3 and C5
   run p4_c3 300 python tools/apply_variants.py --variants 15,20 --blocks 256,512 --nseg 2 --rounds 4

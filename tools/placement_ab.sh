@@ -2,7 +2,7 @@
 # A/B of the placement threshold: default 6100 vs 6260, alternating, main leg + shapes only
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out
-L="--steps 10 --warmup 3 --cpu-baseline 0 --host-path 0 --alloc-probe 0 --c5-leg 0 --c5-bytes 0 --bytes-path 0 --pooled 0 --ceilings 0"
+L="--full --steps 10 --warmup 3 --cpu-baseline 0 --host-path 0 --alloc-probe 0 --c5-leg 0 --c5-bytes 0 --bytes-path 0 --pooled 0 --ceilings 0"
 for rep in 1 2 3; do
   for thr in 6100 6260; do
     echo "=== rep $rep thr $thr" | tee -a gpurun_out/placeab.log
