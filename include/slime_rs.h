@@ -223,6 +223,27 @@ int slime_rs_plan_execute(slime_rs_plan_t plan, const uint32_t *src, slime_rs_la
  * Only before the plan's first launch (SLIME_RS_ERR_INVALID_ARG after it:
  * launches in flight read the table). */
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int *out_shards);
+/* Verify: are the stored shards consistent with the plan?  For every object o
+ * and every output row i, verify reports how many columns would change if the
+ * plan were executed into the compared buffer, and the lowest such column.
+ * cmp is read at the plan's output shard indices (slime_rs_plan_set_outputs)
+ * and may alias src: the common call is one full-slot layout for both and an
+ * encode plan whose outputs are need..total-1.  A column mismatches iff the
+ * word the plan would write (the canonical residue) is not bit-identical to
+ * the stored word, so a stored non-canonical p+3 where 3 is computed counts;
+ * inputs may be any uint32.
+ * Results: two device arrays of nobj x rows uint64, row-major [o][i]:
+ * mismatches[o][i] the exact count, first[o][i] the lowest mismatching column
+ * or UINT64_MAX.  The call initialises both on the stream whenever nobj > 0
+ * (also for L == 0), so the caller never clears them and a captured graph
+ * re-initialises them on every replay (a linear chain: one initialising kernel
+ * node, then one kernel node per 64 plan rows).  Asynchronous; nothing is copied to the host; the call marks
+ * the plan as launched.  Reads src and cmp once and uses no scratch memory.
+ * Codes of up to 16 inputs take the 4-columns-per-lane kernels; wide codes
+ * (k > 16) take the one-column-per-lane form (no matrix-core verify). */
+int slime_rs_plan_verify(slime_rs_plan_t plan, const uint32_t *src, slime_rs_layout_t src_layout,
+                         const uint32_t *cmp, slime_rs_layout_t cmp_layout, uint64_t L, uint64_t nobj,
+                         uint64_t *mismatches, uint64_t *first, void *stream);
 /* Shape of a plan: rows written and inputs read per column. */
 int slime_rs_plan_shape(slime_rs_plan_t plan, int *rows, int *k);
 /* Host copy of the plan's coefficient rows (rows x k, row-major). */
@@ -271,6 +292,20 @@ int slime_rs_resolve_fallbacks_chunked(slime_rs_plan_t encode_plan, uint8_t *slo
 int slime_rs_decode_objects_chunked(slime_rs_plan_t reconstruct_plan, uint8_t *slots, uint64_t slot_stride,
                                     uint64_t chunk_stride, uint64_t L, uint64_t nobj, const uint32_t *mapping,
                                     void *stream);
+/* slime_rs_plan_verify over object slots: for every object o and every output
+ * row i, how many 4-byte columns of chunk out[i] would change if
+ * slime_rs_decode_objects_chunked ran the plan on the slot, and the lowest
+ * such column (BE(stored) != computed ^ mapping[o]).  The plan's inputs and
+ * outputs are chunk indices of the slot: an encode-shaped plan (survivors
+ * 0..need-1, outputs need..total-1) checks a slot's parity.  Layout
+ * preconditions are those of slime_rs_decode_objects_chunked (chunk_stride 0
+ * selects 4L); bytes between 4L and chunk_stride are never read.  Results as
+ * for slime_rs_plan_verify: nobj x rows uint64 each, initialised by the call,
+ * UINT64_MAX in first for none; wide codes take the one-column-per-lane form;
+ * no scratch is used.  Asynchronous. */
+int slime_rs_verify_objects(slime_rs_plan_t plan, const uint8_t *slots, uint64_t slot_stride, uint64_t chunk_stride,
+                            uint64_t L, uint64_t nobj, const uint32_t *mapping, uint64_t *mismatches,
+                            uint64_t *first, void *stream);
 /* encode_objects_chunked that also records the hipEvent_t `phase_event` (may be
  * null) on `stream` between its two passes: after the speculative pass and the
  * mapping selection, before the re-encode of the objects mapped with 1<<31 --

@@ -249,6 +249,36 @@ hipError_t launch_encode_bytes_mfma(const BytesLaunch& a, hipStream_t stream);
 hipError_t launch_decode_bytes_mfma(const BytesLaunch& a, hipStream_t stream);
 hipError_t launch_select_mapping(uint32_t* mapping, uint32_t* status, uint32_t nobj, hipStream_t stream);
 
+// --- device-side verify (rs_verify.hip) -------------------------------------
+// For every object o < nobj and output row i < rows: mismatches[o*rows + i] =
+// the columns b < ncols whose stored word at cmp + o*cmp_obj +
+// out_idx[i]*cmp_shard + 4b differs from the word the plan would write there
+// (the canonical residue of row i over the inputs at in + o*in_obj +
+// in_idx[j]*in_shard + 4b), first[o*rows + i] = the lowest such column or
+// UINT64_MAX.  Strides are in BYTES.  bytes: object slots -- words are
+// big-endian and XOR-ed with mapping[o] (the byte kernels' framing).  The
+// launch initialises both result arrays on the stream itself (also when ncols
+// is 0), reads in and cmp only, and uses no scratch.  k <= 16 with vec_ok runs
+// the 4-columns-per-lane kernels; wider codes and layouts that are not 4-byte
+// aligned run one column per lane.
+struct VerifyLaunch {
+  const void* in;
+  const void* cmp;
+  uint64_t in_obj_stride, in_shard_stride;
+  uint64_t cmp_obj_stride, cmp_shard_stride;
+  const uint32_t* coeff;
+  const uint32_t* in_idx;
+  const uint32_t* out_idx;
+  const uint32_t* mapping = nullptr;  // bytes: nobj mapping values
+  uint64_t* mismatches;
+  uint64_t* first;
+  uint64_t ncols;
+  uint32_t nobj, rows, k;
+  bool vec_ok = true;
+  bool bytes = false;
+};
+hipError_t launch_verify(const VerifyLaunch& v, hipStream_t stream);
+
 // --- small host<->device transfers as one kernel (host_blit.hip) ----------
 // dst/src: device addresses (device memory, or pinned host memory mapped
 // into the device's address space); any alignment.

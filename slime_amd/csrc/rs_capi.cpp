@@ -245,6 +245,24 @@ int execute(const slime_rs_plan* plan, const uint32_t* src, uint64_t src_obj, ui
   return 0;
 }
 
+// The plan's side of a verify launch (slime_rs_plan_verify, slime_rs_verify_objects).
+static VerifyLaunch verify_launch(slime_rs_plan* plan, uint64_t L, uint64_t nobj, uint64_t* mismatches,
+                                  uint64_t* first) {
+  // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
+  plan->executed.store(true, std::memory_order_relaxed);
+  VerifyLaunch v{};
+  v.coeff = plan->d_coeff;
+  v.in_idx = plan->d_in_idx;
+  v.out_idx = plan->d_out_idx;
+  v.mismatches = mismatches;
+  v.first = first;
+  v.ncols = L;
+  v.nobj = (uint32_t)nobj;
+  v.rows = plan->rows;
+  v.k = plan->k;
+  return v;
+}
+
 // The host entry points' plan cache (PlanKey: device, kind, need, total,
 // indices): a bounded LRU (plan_cache.hpp).  Env SLIME_RS_PLAN_CACHE sets the
 // capacity (default 256 plans: at 20/40 a recovery plan's table is about 4 KiB).
@@ -486,6 +504,33 @@ int slime_rs_plan_execute(slime_rs_plan_t plan, const uint32_t* src, slime_rs_la
   if (!src || !dst) return fail(Status::InvalidArg, "plan_execute: null buffer");
   return execute(plan, src, src_layout.obj_stride, src_layout.shard_stride, dst, dst_layout.obj_stride,
                  dst_layout.shard_stride, L, nobj, (hipStream_t)stream);
+}
+
+// Shared by both verify entry points: the result arrays and the object count.
+static int check_verify_results(uint64_t nobj, const uint64_t* mismatches, const uint64_t* first, const char* what) {
+  if (nobj > 0xFFFFFFFFull) return fail(Status::InvalidArg, std::string(what) + ": nobj exceeds 2^32-1");
+  if (!mismatches || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
+  return 0;
+}
+
+int slime_rs_plan_verify(slime_rs_plan_t plan, const uint32_t* src, slime_rs_layout_t src_layout, const uint32_t* cmp,
+                         slime_rs_layout_t cmp_layout, uint64_t L, uint64_t nobj, uint64_t* mismatches,
+                         uint64_t* first, void* stream) {
+  if (!plan) return fail(Status::InvalidArg, "plan_verify: null plan");
+  if (nobj == 0) return 0;
+  if (int rc = check_verify_results(nobj, mismatches, first, "plan_verify")) return rc;
+  if (L != 0 && (!src || !cmp)) return fail(Status::InvalidArg, "plan_verify: null buffer");
+  VerifyLaunch v = verify_launch(plan, L, nobj, mismatches, first);
+  v.in = src;
+  v.cmp = cmp;
+  v.in_obj_stride = 4 * src_layout.obj_stride;
+  v.in_shard_stride = 4 * src_layout.shard_stride;
+  v.cmp_obj_stride = 4 * cmp_layout.obj_stride;
+  v.cmp_shard_stride = 4 * cmp_layout.shard_stride;
+  v.vec_ok = aligned4(src) && aligned4(cmp);  // as slime_rs_plan_execute
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_verify(v, (hipStream_t)stream));
+  return 0;
 }
 
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
@@ -796,6 +841,28 @@ extern "C" int slime_rs_decode_objects_chunked(slime_rs_plan_t plan, uint8_t* sl
 extern "C" int slime_rs_decode_objects(slime_rs_plan_t plan, uint8_t* slots, uint64_t slot_stride, uint64_t L,
                                        uint64_t nobj, const uint32_t* mapping, void* stream) {
   return slime_rs_decode_objects_chunked(plan, slots, slot_stride, 0, L, nobj, mapping, stream);
+}
+
+extern "C" int slime_rs_verify_objects(slime_rs_plan_t plan, const uint8_t* slots, uint64_t slot_stride,
+                                       uint64_t chunk_stride, uint64_t L, uint64_t nobj, const uint32_t* mapping,
+                                       uint64_t* mismatches, uint64_t* first, void* stream) {
+  if (!plan) return fail(Status::InvalidArg, "verify_objects: null plan");
+  if (nobj == 0) return 0;
+  if (int rc = check_verify_results(nobj, mismatches, first, "verify_objects")) return rc;
+  if (L != 0) {  // the layout preconditions of slime_rs_decode_objects_chunked
+    if (!mapping) return fail(Status::InvalidArg, "verify_objects: null mapping");
+    if (int rc = resolve_cstride(L, &chunk_stride, "verify_objects")) return rc;
+    if (int rc = check_slots(plan, slots, slot_stride, chunk_stride, 0, "verify_objects")) return rc;
+  }
+  VerifyLaunch v = verify_launch(plan, L, nobj, mismatches, first);
+  v.in = v.cmp = slots;
+  v.in_obj_stride = v.cmp_obj_stride = slot_stride;
+  v.in_shard_stride = v.cmp_shard_stride = chunk_stride;
+  v.mapping = mapping;
+  v.bytes = true;
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_verify(v, (hipStream_t)stream));
+  return 0;
 }
 
 // ---- device codec / fill ------------------------------------------------------------

@@ -231,6 +231,30 @@ class Plan:
                                           ctypes.c_void_p(dst.data_ptr() + 4 * dst_offset), dst_layout, L, nobj,
                                           _stream_handle(self.device, stream)))
 
+    def verify(self, src: torch.Tensor, src_layout: N.Layout, cmp: torch.Tensor, cmp_layout: N.Layout, L: int,
+               nobj: int, stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+               cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """Check stored shards against the plan without writing them (slime_rs_plan_verify):
+        for every object o and output row i, how many columns would change if the plan were
+        executed into cmp (read at the plan's output shards; may be src itself), and the lowest
+        such column.  Returns (mismatches, first): int64 tensors of shape (nobj, rows) on the
+        plan's device, first == -1 where nothing differs.  Asynchronous, no scratch; the
+        library initialises both results on the stream (capturable into a graph)."""
+        for t in (src, cmp):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan's device")
+        self._check_extent(src, src_offset, src_layout, L, nobj, self.in_max)
+        self._check_extent(cmp, cmp_offset, cmp_layout, L, nobj,
+                           self.rows - 1 if self.out_max is None else self.out_max)
+        mism, first = _verify_results(nobj, self.rows, self.device)
+        N.check(lib.slime_rs_plan_verify(self._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset), src_layout,
+                                         ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset), cmp_layout, L, nobj,
+                                         ctypes.c_void_p(mism.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                                         _stream_handle(self.device, stream)))
+        return mism, first
+
     @staticmethod
     def _check_extent(t: torch.Tensor, off: int, lay: N.Layout, L: int, nobj: int, max_shard: int) -> None:
         # Host-side bounds check before launching a hand-written kernel.
@@ -250,6 +274,13 @@ class Plan:
             self.close()
         except Exception:  # pragma: no cover - interpreter shutdown
             pass
+
+
+def _verify_results(nobj: int, rows: int, device: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """The two (nobj, rows) result tensors of a verify call; the library initialises them."""
+    shape = (nobj, rows)
+    return (torch.empty(shape, dtype=torch.int64, device=f"cuda:{device}"),
+            torch.empty(shape, dtype=torch.int64, device=f"cuda:{device}"))
 
 
 def fill_symbols(t: torch.Tensor, seed: int, stream: Optional[torch.cuda.Stream] = None) -> None:
@@ -360,3 +391,24 @@ def decode_objects(plan: Plan, slots: torch.Tensor, slot_stride: int, L: int, no
     N.check(lib.slime_rs_decode_objects_chunked(plan._h, ctypes.c_void_p(slots.data_ptr()), slot_stride,
                                                 chunk_stride, L, nobj, ctypes.c_void_p(mapping.data_ptr()),
                                                 _stream_handle(dev, stream)))
+
+
+def verify_objects(plan: Plan, slots: torch.Tensor, slot_stride: int, L: int, nobj: int, mapping: torch.Tensor,
+                   stream: Optional[torch.cuda.Stream] = None,
+                   chunk_stride: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """Device scrub of object slots (slime_rs_verify_objects): for every slot o and output row i
+    of the plan, how many 4-byte columns of that output chunk decode_objects would change, and the
+    lowest such column.  An encode-shaped plan (survivors 0..need-1, outputs need..total-1) checks
+    a slot's parity chunks.  Returns (mismatches, first) as Plan.verify does; nothing is written
+    to the slots and bytes between 4L and chunk_stride are never read."""
+    hi = max(plan.in_max, plan.rows - 1 if plan.out_max is None else plan.out_max)
+    dev = _check_slots(slots, slot_stride, nobj, _chunk_stride(L, chunk_stride) * (hi + 1))
+    if mapping.numel() < nobj or mapping.dtype not in (torch.int32, torch.uint32) or _dev_index(mapping) != dev:
+        raise ValueError("mapping needs nobj int32 words on the slots' device")
+    if dev != plan.device:
+        raise ValueError("slots are not on the plan's device")
+    mism, first = _verify_results(nobj, plan.rows, dev)
+    N.check(lib.slime_rs_verify_objects(plan._h, ctypes.c_void_p(slots.data_ptr()), slot_stride, chunk_stride, L,
+                                        nobj, ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(mism.data_ptr()),
+                                        ctypes.c_void_p(first.data_ptr()), _stream_handle(dev, stream)))
+    return mism, first
