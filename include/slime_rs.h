@@ -250,6 +250,58 @@ int slime_rs_plan_shape(slime_rs_plan_t plan, int *rows, int *k);
 int slime_rs_plan_coefficients(slime_rs_plan_t plan, uint32_t *out);
 int slime_rs_plan_destroy(slime_rs_plan_t plan);
 
+/* ---- ragged batches: one launch over objects of different lengths ----------
+ * A span places one object: its shard s is read at src + src_off +
+ * s*src_shard_stride and written at dst + dst_off + s*dst_shard_stride (all in
+ * uint32 elements, shard indices as the plan gives them), L symbols per shard.
+ * L == 0 is allowed (the object is skipped). */
+typedef struct slime_rs_span {
+  uint64_t src_off;          /* uint32 elements from the launch's src to this object's shard 0 */
+  uint64_t src_shard_stride; /* elements between its shards in src */
+  uint64_t dst_off;          /* the same two for dst */
+  uint64_t dst_shard_stride;
+  uint64_t L;                /* symbols per shard */
+} slime_rs_span_t;
+
+typedef struct slime_rs_batch *slime_rs_batch_t;
+
+/* Host array of nobj spans -> a device-resident work table for plans with k
+ * inputs on `device`.  Synchronous.  A batch is bound to (device, k), not to a
+ * plan: one batch serves the encode plan and every reconstruct plan of a code.
+ * Refused with SLIME_RS_ERR_INVALID_ARG: null arguments, k <= 0, any L of 2^30
+ * or more (shards of a ragged batch stay under 4 GiB; slime_rs_plan_execute
+ * remains for larger ones), nobj or a work-unit count of 2^32 or more.  nobj
+ * == 0, or every L == 0, gives a valid empty batch.  The tables take 64 bytes
+ * per object, 8 per unit of up to 1536 (k > 4) or 3072 (k <= 4) columns and 8
+ * per column of L % 4. */
+int slime_rs_batch_create(int device, int k, const slime_rs_span_t *spans, uint64_t nobj, slime_rs_batch_t *batch);
+/* Objects, columns (the sum of L) and work units of a batch; any output may be NULL. */
+int slime_rs_batch_info(slime_rs_batch_t batch, uint64_t *nobj, uint64_t *columns, uint64_t *units);
+/* Frees the tables with hipFree, which waits for the device (as
+ * slime_rs_plan_destroy does): launches in flight finish first.  Not inside a
+ * graph capture; a graph that captured a launch of the batch must be destroyed
+ * before it. */
+int slime_rs_batch_destroy(slime_rs_batch_t batch);
+/* out[o][out_idx[i]][b] = sum_j coeff[i][j] * in[o][in_idx[j]][b] for every
+ * span o of the batch and b < L_o, in ONE launch; bit-identical to
+ * slime_rs_plan_execute run object by object.  Asynchronous.  The launch reads
+ * device memory only (the batch's and the plan's tables, src, dst), so it is
+ * capturable under exactly the rules of slime_rs_plan_execute
+ * (slime_rs_kernel_schedule); it marks the plan as launched.  The plan's k and
+ * device must be the batch's (SLIME_RS_ERR_INVALID_ARG).  An empty batch
+ * launches nothing and returns 0.  dst may be src with the outputs in each
+ * object's own slots; outputs of different objects that overlap each other or
+ * another object's inputs are undefined, like overlapping layouts.
+ * Forms: plans of up to 16 inputs over 4-byte aligned src and dst run the
+ * 4-columns-per-lane kernel (dynamic schedule, or static where
+ * slime_rs_plan_execute would take it); wider plans, and bases that are not
+ * 4-byte aligned, run one column per lane (correct, not fast: there is no
+ * matrix-core or k-template ragged kernel).  Also out of scope: ragged forms
+ * of the byte-slot pipeline and of verify, and per-object plans (group the
+ * objects by erasure pattern, one batch per group). */
+int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
+                                void *stream);
+
 /* ==== fused byte-domain object pipeline (writeChunks / reconstruct on device) ====
  * Object slots: object o's slot starts at slots + o*slot_stride bytes and holds
  * its `total` chunks of 4L bytes (chunk c at slot + c*4L, L = ceil(ceil(S/4)/need),

@@ -65,6 +65,12 @@ class Layout(ctypes.Structure):
     _fields_ = [("obj_stride", ctypes.c_uint64), ("shard_stride", ctypes.c_uint64)]
 
 
+class Span(ctypes.Structure):
+    """slime_rs_span_t: one object of a ragged batch (offsets and strides in uint32 elements)."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("src_shard_stride", ctypes.c_uint64), ("dst_off", ctypes.c_uint64),
+                ("dst_shard_stride", ctypes.c_uint64), ("L", ctypes.c_uint64)]
+
+
 # (name, restype, argtypes) for every symbol include/slime_rs.h declares.
 SIGNATURES = [
     ("slime_rs_status_string", ctypes.c_char_p, [ctypes.c_int]),
@@ -115,6 +121,12 @@ SIGNATURES = [
     ("slime_rs_plan_verify", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, Layout, ctypes.c_void_p, Layout, ctypes.c_uint64, ctypes.c_uint64,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("slime_rs_batch_create", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]),
+    ("slime_rs_batch_info", ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p]),
+    ("slime_rs_batch_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("slime_rs_plan_execute_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("slime_rs_verify_objects", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -44,6 +44,19 @@ struct slime_rs_plan {
   bool in_seq = false;                 // in_idx is 0..k-1 (encode plans)
 };
 
+// The device work tables of a ragged batch (slime_rs_batch_t): ragged_plan.hpp's
+// three tables, each in its own allocation (scalar loads ignore low address
+// bits: every table starts on hipMalloc's alignment), cut by the geometry of k.
+struct slime_rs_batch {
+  int device = 0;
+  uint32_t k = 0;
+  slime::ragged::Geometry g{1, 1};
+  slime::ragged::Counts counts;
+  slime::ragged::Desc* d_desc = nullptr;
+  slime::ragged::Unit* d_units = nullptr;
+  slime::ragged::Tail* d_tails = nullptr;
+};
+
 namespace slime {
 
 // ---- thread state (rs_capi.cpp) ----------------------------------------------

@@ -8,6 +8,8 @@
 
 #include <functional>
 
+#include "ragged_plan.hpp"
+
 namespace slime {
 
 // One matrix application over a batch of objects:
@@ -138,6 +140,17 @@ inline uint64_t queue_blocks(uint64_t full, uint64_t units) {
 // (tools/c2_stamps.py).
 // 0 when the launch has too many units for 32-bit tickets, or at most one
 // block's (below): the caller takes the static kernel.
+// Units up to which a launch takes the static kernels (env SLIME_RS_TINY_UNITS,
+// default 4; 0 = off): see queue_spread.
+inline uint64_t tiny_queue_units() {
+  static const uint64_t tiny = [] {
+    const char* e = getenv("SLIME_RS_TINY_UNITS");
+    const long long v = e ? atoll(e) : 4;
+    return v > 0 ? (uint64_t)v : 0ull;
+  }();
+  return tiny;
+}
+
 inline uint32_t queue_spread(uint32_t nobj, uint64_t ncols, int U, int C, uint32_t streams = 0) {
   const uint64_t ntiles = ((ncols >> 2) + 64ull * U - 1) / (64ull * U);
   const uint64_t groups = (ntiles + 4ull * C - 1) / (4ull * C);
@@ -158,11 +171,7 @@ inline uint32_t queue_spread(uint32_t nobj, uint64_t ncols, int U, int C, uint32
   // reconstruct equal or better: profiles/r04/s50_tinyab2, s51_tinyab3; env
   // SLIME_RS_ONE_OBJECT_UNITS, default 1024; 0 = off).  Batches of several
   // objects keep the queue from 5 units up.
-  static const uint64_t tiny = [] {
-    const char* e = getenv("SLIME_RS_TINY_UNITS");
-    const long long v = e ? atoll(e) : 4;
-    return v > 0 ? (uint64_t)v : 0ull;
-  }();
+  const uint64_t tiny = tiny_queue_units();
   static const uint64_t one_object = [] {
     const char* e = getenv("SLIME_RS_ONE_OBJECT_UNITS");
     const long long v = e ? atoll(e) : 1024;
@@ -278,6 +287,33 @@ struct VerifyLaunch {
   bool bytes = false;
 };
 hipError_t launch_verify(const VerifyLaunch& v, hipStream_t stream);
+
+// --- ragged batches (rs_ragged.hip) ------------------------------------------
+// One matrix application over objects of different lengths: object o's
+// offsets, strides and length come from desc[o], the work from the unit and
+// tail lists (ragged_plan.hpp; all three device tables, cut by the geometry
+// U, C = ragged::geometry_for_k(k)).  For every object and b < L_o:
+//   out[dst_off + out_idx[i]*dst_shard + b] = sum_j coeff[i][j] * in[src_off + in_idx[j]*src_shard + b]
+// k <= 16 with vec_ok runs the 4-columns-per-lane kernel on the dynamic or
+// the static schedule, as launch_apply chooses between them; wider codes and
+// bases that are not 4-byte aligned run one column per lane.  Reads device
+// memory only: capturable under launch_apply's rules.
+struct RaggedLaunch {
+  const uint32_t* in;
+  uint32_t* out;
+  const ragged::Desc* desc;
+  const ragged::Unit* units;
+  const ragged::Tail* tails;
+  uint32_t nunits;
+  uint64_t ntails;
+  int U, C;
+  const uint32_t* coeff;
+  const uint32_t* in_idx;
+  const uint32_t* out_idx;
+  uint32_t rows, k;
+  bool vec_ok;
+};
+hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t stream);
 
 // --- small host<->device transfers as one kernel (host_blit.hip) ----------
 // dst/src: device addresses (device memory, or pinned host memory mapped

@@ -506,6 +506,109 @@ int slime_rs_plan_execute(slime_rs_plan_t plan, const uint32_t* src, slime_rs_la
                  dst_layout.shard_stride, L, nobj, (hipStream_t)stream);
 }
 
+// ---- ragged batches (ragged_plan.hpp, rs_ragged.hip) -----------------------------
+
+static_assert(sizeof(slime_rs_span_t) == sizeof(ragged::Span) && offsetof(slime_rs_span_t, L) == offsetof(ragged::Span, L),
+              "slime_rs_span_t is ragged::Span");
+
+static void free_batch_tables(slime_rs_batch* b) {
+  if (b->d_desc) (void)hipFree(b->d_desc);
+  if (b->d_units) (void)hipFree(b->d_units);
+  if (b->d_tails) (void)hipFree(b->d_tails);
+  b->d_desc = nullptr;
+  b->d_units = nullptr;
+  b->d_tails = nullptr;
+}
+
+// One table into an allocation of its own (empty tables stay null).
+static hipError_t upload_table(const void* host, size_t bytes, void** dev) {
+  if (!bytes) return hipSuccess;
+  if (hipError_t e = hipMalloc(dev, bytes)) return e;  // the caller frees it on any later failure
+  return hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice);
+}
+
+int slime_rs_batch_create(int device, int k, const slime_rs_span_t* spans, uint64_t nobj, slime_rs_batch_t* batch) {
+  if (!batch) return fail(Status::InvalidArg, "batch_create: null batch");
+  *batch = nullptr;
+  if (k <= 0) return fail(Status::InvalidArg, "batch_create: k must be positive");
+  if (!spans && nobj) return fail(Status::InvalidArg, "batch_create: null spans");
+  const ragged::Geometry g = ragged::geometry_for_k(k);
+  const ragged::Span* sp = reinterpret_cast<const ragged::Span*>(spans);
+  std::string why;
+  ragged::Counts counts;
+  if (!ragged::count(sp, nobj, g, &counts, &why)) return fail(Status::InvalidArg, "batch_create: " + why);
+  if (int rc = check_device(device)) return rc;
+  ragged::Tables t;
+  if (!ragged::build(sp, nobj, g, &t, &why)) return fail(Status::InvalidArg, "batch_create: " + why);
+  auto b = std::make_unique<slime_rs_batch>();
+  b->device = device;
+  b->k = (uint32_t)k;
+  b->g = g;
+  b->counts = t.counts;
+  DeviceScope ds(device);
+  hipError_t e = upload_table(t.desc.data(), t.desc.size() * sizeof(ragged::Desc), (void**)&b->d_desc);
+  if (e == hipSuccess) e = upload_table(t.units.data(), t.units.size() * sizeof(ragged::Unit), (void**)&b->d_units);
+  if (e == hipSuccess) e = upload_table(t.tails.data(), t.tails.size() * sizeof(ragged::Tail), (void**)&b->d_tails);
+  // The device's first ticket-counter sets, outside any capture (as build_plan).
+  if (e == hipSuccess) e = warm_ticket_pool(device);
+  if (e != hipSuccess) {
+    free_batch_tables(b.get());
+    return fail_hip(e, "batch_create: work tables");
+  }
+  *batch = b.release();
+  return 0;
+}
+
+int slime_rs_batch_info(slime_rs_batch_t batch, uint64_t* nobj, uint64_t* columns, uint64_t* units) {
+  if (!batch) return fail(Status::InvalidArg, "batch_info: null batch");
+  if (nobj) *nobj = batch->counts.nobj;
+  if (columns) *columns = batch->counts.columns;
+  if (units) *units = batch->counts.units;
+  return 0;
+}
+
+int slime_rs_batch_destroy(slime_rs_batch_t batch) {
+  if (!batch) return fail(Status::InvalidArg, "batch_destroy: null batch");
+  {
+    DeviceScope ds(batch->device);
+    free_batch_tables(batch);  // hipFree waits for the device: launches in flight have finished
+  }
+  delete batch;
+  return 0;
+}
+
+int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
+                                void* stream) {
+  if (!plan) return fail(Status::InvalidArg, "plan_execute_batch: null plan");
+  if (!batch) return fail(Status::InvalidArg, "plan_execute_batch: null batch");
+  if (plan->k != batch->k || plan->device != batch->device)
+    return fail(Status::InvalidArg, "plan_execute_batch: the batch was created for k = " + std::to_string(batch->k) +
+                                        " on device " + std::to_string(batch->device) + ", the plan has k = " +
+                                        std::to_string(plan->k) + " on device " + std::to_string(plan->device));
+  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (!src || !dst) return fail(Status::InvalidArg, "plan_execute_batch: null buffer");
+  RaggedLaunch a;
+  a.in = src;
+  a.out = dst;
+  a.desc = batch->d_desc;
+  a.units = batch->d_units;
+  a.tails = batch->d_tails;
+  a.nunits = (uint32_t)batch->counts.units;
+  a.ntails = batch->counts.tails;
+  a.U = batch->g.U;
+  a.C = batch->g.C;
+  a.coeff = plan->d_coeff;
+  a.in_idx = plan->d_in_idx;
+  a.out_idx = plan->d_out_idx;
+  a.rows = plan->rows;
+  a.k = plan->k;
+  a.vec_ok = aligned4(src) && aligned4(dst);  // as slime_rs_plan_execute
+  plan->executed.store(true, std::memory_order_relaxed);
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_apply_ragged(a, (hipStream_t)stream));
+  return 0;
+}
+
 // Shared by both verify entry points: the result arrays and the object count.
 static int check_verify_results(uint64_t nobj, const uint64_t* mismatches, const uint64_t* first, const char* what) {
   if (nobj > 0xFFFFFFFFull) return fail(Status::InvalidArg, std::string(what) + ": nobj exceeds 2^32-1");

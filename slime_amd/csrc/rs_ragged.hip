@@ -1,0 +1,392 @@
+// Ragged batches for CDNA4 (gfx950): one launch of a plan over objects of
+// different lengths at arbitrary offsets (slime_rs_plan_execute_batch).  The
+// arithmetic and the tile loads and stores are rs_apply_kernel.hpp's
+// (load_tile, store_tile, apply_column); what is new is where a wave's work
+// comes from.  The host (ragged_plan.hpp) cuts every object into units of up
+// to C consecutive tiles of 256 U columns and lists them, {object, first
+// tile}, in device memory beside one 64-byte descriptor per object; a unit
+// never crosses an object, and the list goes round the objects four units at
+// a time.
+//
+// Forms (a batch serves every plan with its k inputs on its device):
+//   k <= 16, 4-byte aligned src and dst: rs_apply_ragged_kernel<K, U, C>, four
+//     columns a lane, U and C as the dynamic-schedule apply launch picks them
+//     for K.  DYN: units are tickets drawn from the eight per-XCD counters of
+//     a counter set exactly as TicketWalk draws them (rs_apply_kernel.hpp:
+//     empty partitions passed over, the exit counter, the last wave out zeroes
+//     the set); ticket l of partition p is list entry ((l / 4) NC + p) 4 + l % 4,
+//     so the four waves that take consecutive tickets sweep four consecutive
+//     units of one object, and the next group belongs to the next object.  Static (schedule mode 0, captures under mode 1, no counter set
+//     to be had, batches of at most SLIME_RS_TINY_UNITS units): wave w takes
+//     entries w, w + nwaves, ...  Both double-buffered; slime_rs_kernel_pipeline(0)
+//     runs the static walk one tile at a time.
+//   k > 16, or a base that is not 4-byte aligned: rs_apply_ragged_column_kernel,
+//     one column per lane through apply::wide_dot over the same unit list
+//     (static walk).  Correct for any k a plan allows; matrix-core and
+//     k-template ragged kernels are out of scope.
+//
+// The walk keeps two things in flight: the ticket for the unit after the
+// next (an atomic, lane 0) and the list entry of the next unit (one 8-byte
+// scalar load), each issued a unit before it is read.  On entering a unit of
+// another object the wave takes that object's descriptor (one
+// s_load_dwordx16) and recomputes its K input bases and its output base,
+// wave-uniform SGPR pairs; inside the double-buffered loop nothing else
+// differs from rs_apply_queue_kernel: loads are unconditional, lanes past the
+// object's last vector re-read it, the prefetch past a wave's last unit
+// re-reads its current tile.
+//
+// Columns past each object's last whole vector (L % 4; all of an object of
+// fewer than 4 columns) are {object, column} items strided over the grid
+// after the walk, one per lane, through apply_column<K>.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+#include "rs_apply_kernel.hpp"
+
+namespace slime {
+namespace ragged {
+
+using apply::kBlock;
+using apply::kTicketStride;
+using apply::kWaves;
+using apply::u32x16;
+
+// A descriptor's live fields in SGPRs.
+struct ObjRef {
+  uint64_t src_off, src_shard, dst_off, dst_shard;
+  uint32_t nvec, ntiles;
+};
+__device__ __forceinline__ ObjRef load_desc(const Desc* __restrict__ descs, uint32_t obj) {
+  const u32x16 v = *reinterpret_cast<const u32x16*>(descs + obj);  // one 64-byte entry
+  ObjRef r;
+  r.src_off = v[0] | ((uint64_t)v[1] << 32);
+  r.src_shard = v[2] | ((uint64_t)v[3] << 32);
+  r.dst_off = v[4] | ((uint64_t)v[5] << 32);
+  r.dst_shard = v[6] | ((uint64_t)v[7] << 32);
+  r.nvec = v[8];
+  r.ntiles = v[9];
+  return r;
+}
+
+// A wave's walk over the unit list (device state, wave-uniform), with
+// TicketWalk's interface: obj, tile(), advance(), live, finish() -- and d,
+// the current object's descriptor, with `fresh` set while the current tile is
+// the first since d changed.
+template <int C, int NC, bool DYN>
+struct UnitWalk {
+  uint32_t* ticket;
+  const Unit* __restrict__ list;
+  const Desc* __restrict__ descs;
+  uint32_t n, ngrp, lane;          // list entries; groups of four entries, ceil(n / 4)
+  uint32_t p = 0, dry = 0, pend = 0;  // DYN: partition, partitions found dry, pending atomic
+  uint32_t e = 0, step = 0;           // static: the entry loaded ahead, the wave count
+  uint32_t a_obj = 0, a_tile = 0;     // the next unit's entry (loaded a unit ahead)
+  bool a_ok = false;
+  ObjRef d{};
+  uint32_t d_obj = ~0u;
+  bool fresh = false;
+  uint32_t obj = 0, tb = 0, cnt = 0, i = 0;  // current unit
+  bool live = true;
+
+  // first / step_: the wave's index and the launch's wave count (static walk).
+  __device__ __forceinline__ UnitWalk(uint32_t* t, const Unit* __restrict__ list_, const Desc* __restrict__ descs_,
+                                      uint32_t n_, uint32_t lane_, uint32_t first, uint32_t step_)
+      : ticket(t), list(list_), descs(descs_), n(n_), ngrp(list_groups(n_)), lane(lane_) {
+    uint32_t en = 0;
+    if constexpr (DYN) {
+      p = hw_xcc() % NC;
+      a_ok = skip_empty();
+      if (a_ok) {
+        request();
+        a_ok = draw(en);
+      }
+    } else {
+      step = step_;
+      e = first;
+      a_ok = e < n;
+      en = e;
+    }
+    if (a_ok) load_ahead(en);
+    next_unit();
+  }
+  __device__ __forceinline__ static uint32_t hw_xcc() { return apply::hw_xcc_id(); }
+  // TicketWalk::skip_empty: partition p holds units iff p < ngrp.
+  __device__ __forceinline__ bool skip_empty() {
+    if (p < ngrp) return true;
+    dry += NC - p;
+    p = 0;
+    return ngrp != 0 && dry < NC;  // false: every partition is dry
+  }
+  __device__ __forceinline__ void request() {
+    pend = 0;
+    if (lane == 0) pend = atomicAdd(ticket + p * kTicketStride, 1u);
+  }
+  // The list index of the pending ticket (or of a later one: dry partitions
+  // and the last group's missing entries are passed over), and the request of
+  // the ticket after it.  false: every partition is dry, no draw is pending.
+  __device__ __forceinline__ bool draw(uint32_t& en) {
+    for (;;) {
+      const uint32_t l = __builtin_amdgcn_readlane(pend, 0);  // lane 0 drew it, whatever the exec mask
+      if (l >= partition_tickets(ngrp, p, NC)) {
+        if (++dry >= NC) return false;
+        p = p + 1 == NC ? 0 : p + 1;
+        if (!skip_empty()) return false;
+        request();
+        continue;
+      }
+      request();
+      en = ticket_entry(l, p, NC);
+      if (en < n) return true;
+    }
+  }
+  __device__ __forceinline__ void load_ahead(uint32_t en) {
+    const uint2 v = *reinterpret_cast<const uint2*>(list + en);  // one 8-byte scalar load
+    a_obj = v.x;
+    a_tile = v.y;
+  }
+  // Enter the unit loaded ahead, and fetch the entry of the one after it.
+  __device__ __forceinline__ void next_unit() {
+    if (!a_ok) {
+      live = false;
+      return;
+    }
+    obj = a_obj;
+    tb = a_tile;
+    i = 0;
+    uint32_t en = 0;
+    if constexpr (DYN) {
+      a_ok = draw(en);
+    } else {
+      a_ok = n - e > step;  // e + step < n, no wrap
+      e += step;
+      en = e;
+    }
+    if (a_ok) load_ahead(en);
+    if (obj != d_obj) {
+      d = load_desc(descs, obj);
+      d_obj = obj;
+      fresh = true;
+    }
+    cnt = d.ntiles - tb < (uint32_t)C ? d.ntiles - tb : (uint32_t)C;  // the host lists tb < ntiles only
+  }
+  __device__ __forceinline__ uint32_t tile() const { return tb + i; }
+  __device__ __forceinline__ void advance() {
+    fresh = false;
+    if (++i >= cnt) next_unit();
+  }
+  // TicketWalk::finish: once per wave after the walk ended; the launch's last
+  // wave out returns the counter set to zero.
+  __device__ __forceinline__ void finish() {
+    if constexpr (DYN) {
+      if (lane == 0) {
+        uint32_t* const done = ticket + NC * kTicketStride;
+        if (atomicAdd(done, 1u) == gridDim.x * gridDim.y * (blockDim.x >> 6) - 1) {
+#pragma unroll
+          for (int q = 0; q < NC; ++q) atomicExch(ticket + q * kTicketStride, 0u);
+          atomicExch(done, 0u);
+        }
+      }
+    }
+  }
+};
+
+// Where a loaded tile goes: its object's output base and stride, the
+// object's vector count and the lane's first vector.
+struct TileOut {
+  uint32_t* ob;
+  uint64_t shard;
+  uint32_t nvec, g0;
+};
+
+// The {object, column} items past the objects' last whole vectors, strided
+// over the grid, one per lane (K == 0: generic k).
+template <int K>
+__device__ __forceinline__ void ragged_tails(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                             const Desc* __restrict__ descs, const Tail* __restrict__ tails,
+                                             uint64_t ntails, const uint32_t* __restrict__ coeff,
+                                             const uint32_t* __restrict__ in_idx,
+                                             const uint32_t* __restrict__ out_idx, uint32_t rows, uint32_t k) {
+  const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint64_t nthr = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t t = tid; t < ntails; t += nthr) {
+    const Tail it = tails[t];
+    const Desc* const d = descs + it.obj;
+    apply::apply_column<K>(in + d->src_off, out + d->dst_off, coeff, in_idx, d->src_shard, out_idx, d->dst_shard,
+                           rows, k, (uint64_t)it.col);
+  }
+}
+
+template <int K, int U, int C, int NC, bool NTL, bool NTS, bool DYN, bool PIPE>
+__global__ __launch_bounds__(kBlock) void rs_apply_ragged_kernel(
+    const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const Desc* __restrict__ descs,
+    const Unit* __restrict__ units, const Tail* __restrict__ tails, const uint32_t* __restrict__ coeff,
+    const uint32_t* __restrict__ in_idx, const uint32_t* __restrict__ out_idx, uint32_t nunits, uint64_t ntails,
+    uint32_t rows, uint32_t k, uint32_t* __restrict__ ticket) {
+  static_assert(K > 0 && K <= 16 && NC > 0 && NC <= 64, "compile-time k only");
+  static_assert(PIPE || !DYN, "the dynamic walk is double-buffered");
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  UnitWalk<C, NC, DYN> w(ticket, units, descs, nunits, lane, wave, gridDim.x * kWaves);
+  const uint32_t* sb[K];
+  auto bases = [&]() {
+#pragma unroll
+    for (int j = 0; j < K; ++j) sb[j] = in + w.d.src_off + (uint64_t)in_idx[j] * w.d.src_shard;
+  };
+  auto here = [&]() { return TileOut{out + w.d.dst_off, w.d.dst_shard, w.d.nvec, w.tile() * (64 * U) + lane}; };
+  if constexpr (PIPE) {
+    if (w.live) {
+      uint4 xa[U][K], xb[U][K];
+      bases();
+      TileOut ta = here(), tb = ta;
+      apply::load_tile<K, U, NTL>(xa, sb, ta.g0, ta.nvec);
+      for (;;) {
+        w.advance();
+        // Past the last unit the prefetch re-reads the current tile (unconditional loads, see load_tile).
+        tb = ta;
+        if (w.live) {
+          if (w.fresh) bases();
+          tb = here();
+        }
+        apply::load_tile<K, U, NTL>(xb, sb, tb.g0, tb.nvec);
+        apply::store_tile<K, U, NTS>(xa, ta.ob, coeff, out_idx, ta.shard, rows, ta.g0, ta.nvec);
+        if (!w.live) break;
+        w.advance();
+        ta = tb;
+        if (w.live) {
+          if (w.fresh) bases();
+          ta = here();
+        }
+        apply::load_tile<K, U, NTL>(xa, sb, ta.g0, ta.nvec);
+        apply::store_tile<K, U, NTS>(xb, tb.ob, coeff, out_idx, tb.shard, rows, tb.g0, tb.nvec);
+        if (!w.live) break;
+      }
+    }
+  } else {
+    while (w.live) {
+      uint4 x[U][K];
+      if (w.fresh) bases();
+      const TileOut t = here();
+      apply::load_tile<K, U, NTL>(x, sb, t.g0, t.nvec);
+      apply::store_tile<K, U, NTS>(x, t.ob, coeff, out_idx, t.shard, rows, t.g0, t.nvec);
+      w.advance();
+    }
+  }
+  w.finish();
+  ragged_tails<K>(in, out, descs, tails, ntails, coeff, in_idx, out_idx, rows, k);
+}
+
+// One column per lane over the same unit list (static walk): generic k
+// through wide_dot, any alignment.  tile_cols = 256 U, unit_tiles = C of the
+// batch's geometry.
+__global__ __launch_bounds__(kBlock) void rs_apply_ragged_column_kernel(
+    const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const Desc* __restrict__ descs,
+    const Unit* __restrict__ units, const Tail* __restrict__ tails, const uint32_t* __restrict__ coeff,
+    const uint32_t* __restrict__ in_idx, const uint32_t* __restrict__ out_idx, uint32_t nunits, uint64_t ntails,
+    uint32_t rows, uint32_t k, uint32_t tile_cols, uint32_t unit_tiles) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t nwaves = gridDim.x * kWaves;
+  for (uint64_t e = wave; e < nunits; e += nwaves) {
+    const Unit u = units[e];
+    const ObjRef d = load_desc(descs, u.obj);
+    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
+    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)d.nvec << 2;
+    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+    for (uint64_t b = b0 + lane; b < b1; b += 64)
+      apply::apply_column<0>(in + d.src_off, out + d.dst_off, coeff, in_idx, d.src_shard, out_idx, d.dst_shard, rows,
+                             k, b);
+  }
+  ragged_tails<0>(in, out, descs, tails, ntails, coeff, in_idx, out_idx, rows, k);
+}
+
+}  // namespace ragged
+
+namespace {
+
+using apply::kBlock;
+constexpr bool kNtLoads = true;
+constexpr bool kNtStores = true;
+constexpr uint64_t kQueueBlocks = 256;  // one block per CU, as launch_queue (rs_apply.hip)
+
+// Blocks of a ragged launch: one wave per unit up to `full` (queue_blocks),
+// and enough lanes for the tail items of a batch of many short objects.
+uint64_t ragged_blocks(uint64_t full, const RaggedLaunch& a) {
+  const uint64_t by_units = queue_blocks(full, a.nunits);
+  const uint64_t by_tails = (a.ntails + kBlock - 1) / kBlock;
+  const uint64_t want = by_tails < full ? by_tails : full;
+  return by_units > want ? by_units : want;
+}
+
+#define SLIME_RAGGED_ARGS(a) \
+  (a).in, (a).out, (a).desc, (a).units, (a).tails, (a).coeff, (a).in_idx, (a).out_idx, (a).nunits, (a).ntails, \
+      (a).rows, (a).k
+
+template <int K, bool PIPE>
+hipError_t launch_static(const RaggedLaunch& a, hipStream_t s) {
+  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
+  // The static pipelined apply launch's block budget (rs_apply.hip, pipe_blocks).
+  const uint64_t blocks = ragged_blocks(K <= 12 ? 256 : 1024, a);
+  hipLaunchKernelGGL((ragged::rs_apply_ragged_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, false, PIPE>),
+                     dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_RAGGED_ARGS(a), nullptr);
+  return hipGetLastError();
+}
+
+template <int K>
+hipError_t dispatch(const RaggedLaunch& a, hipStream_t s) {
+  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
+  if (!pipelined_kernels()) return launch_static<K, false>(a, s);
+  // The dynamic schedule has nothing to balance over one block's units (queue_spread, kernels.hpp).
+  if (queue_allowed(s) && a.nunits > tiny_queue_units()) {
+    bool launched = false;
+    const uint64_t blocks = ragged_blocks(kQueueBlocks, a);
+    const hipError_t e = with_tickets(
+        s,
+        [&](uint32_t* set) {
+          hipLaunchKernelGGL((ragged::rs_apply_ragged_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, true, true>),
+                             dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_RAGGED_ARGS(a), set);
+          return hipGetLastError();
+        },
+        &launched);
+    if (launched || e != hipSuccess) return e;
+  }
+  return launch_static<K, true>(a, s);
+}
+
+hipError_t launch_columns(const RaggedLaunch& a, hipStream_t s) {
+  const uint64_t blocks = ragged_blocks(1024, a);
+  hipLaunchKernelGGL(ragged::rs_apply_ragged_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                     SLIME_RAGGED_ARGS(a), 256u * (uint32_t)a.U, (uint32_t)a.C);
+  return hipGetLastError();
+}
+
+#undef SLIME_RAGGED_ARGS
+
+}  // namespace
+
+hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t s) {
+  (void)hipGetLastError();  // report only this launch's error, not one left on the thread
+  if ((a.nunits == 0 && a.ntails == 0) || a.rows == 0) return hipSuccess;
+  if (a.k > 16 || !a.vec_ok) return launch_columns(a, s);
+  // The vector kernels are instantiated with the geometry of their K: the tables must be cut by it.
+  if (a.U != ragged::unroll_for_k((int)a.k) || a.C != ragged::unit_tiles_for_k((int)a.k)) return hipErrorInvalidValue;
+  switch (a.k) {
+    case 1: return dispatch<1>(a, s);
+    case 2: return dispatch<2>(a, s);
+    case 3: return dispatch<3>(a, s);
+    case 4: return dispatch<4>(a, s);
+    case 5: return dispatch<5>(a, s);
+    case 6: return dispatch<6>(a, s);
+    case 7: return dispatch<7>(a, s);
+    case 8: return dispatch<8>(a, s);
+    case 9: return dispatch<9>(a, s);
+    case 10: return dispatch<10>(a, s);
+    case 11: return dispatch<11>(a, s);
+    case 12: return dispatch<12>(a, s);
+    case 13: return dispatch<13>(a, s);
+    case 14: return dispatch<14>(a, s);
+    case 15: return dispatch<15>(a, s);
+    default: return dispatch<16>(a, s);
+  }
+}
+
+}  // namespace slime

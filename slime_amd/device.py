@@ -255,6 +255,28 @@ class Plan:
                                          _stream_handle(self.device, stream)))
         return mism, first
 
+    def execute_batch(self, src: torch.Tensor, dst: torch.Tensor, batch: "Batch",
+                      stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0, dst_offset: int = 0) -> None:
+        """One launch over a ragged batch (slime_rs_plan_execute_batch): every span of `batch`, each
+        with its own offsets, strides and length; offsets are in uint32 elements from the tensors'
+        starts.  dst may be src (outputs in each object's own slots).  Asynchronous."""
+        for t in (src, dst):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan's device")
+        if batch.device != self.device or batch.k != self.k:
+            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
+                             f"the plan has k={self.k} on device {self.device}")
+        batch._check_extent(src, src_offset, 0, self.in_max)
+        batch._check_extent(dst, dst_offset, 1, self.rows - 1 if self.out_max is None else self.out_max)
+        _note_unprobed(src)
+        if dst.data_ptr() != src.data_ptr():
+            _note_unprobed(dst)
+        N.check(lib.slime_rs_plan_execute_batch(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                                                ctypes.c_void_p(dst.data_ptr() + 4 * dst_offset),
+                                                _stream_handle(self.device, stream)))
+
     @staticmethod
     def _check_extent(t: torch.Tensor, off: int, lay: N.Layout, L: int, nobj: int, max_shard: int) -> None:
         # Host-side bounds check before launching a hand-written kernel.
@@ -267,6 +289,66 @@ class Plan:
     def close(self) -> None:
         if self._h:
             lib.slime_rs_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
+class Batch:
+    """A ragged batch (slime_rs_batch_t): objects of different lengths at arbitrary offsets, as a
+    device-resident work table for the plans with k inputs on one device.  One batch serves the
+    encode plan and every reconstruct plan of a code (Plan.execute_batch).
+
+    spans: one (src_off, src_shard_stride, dst_off, dst_shard_stride, L) per object, in uint32
+    elements; L < 2**30, L == 0 is skipped."""
+
+    def __init__(self, spans, k: int, device: int = 0):
+        self._h = None
+        self.spans = np.ascontiguousarray(np.asarray(spans, dtype=np.uint64).reshape(-1, 5))
+        self.k, self.device = int(k), int(device)
+        self._extents: dict = {}
+        h = ctypes.c_void_p()
+        N.check(lib.slime_rs_batch_create(self.device, self.k, self.spans.ctypes.data if len(self.spans) else None,
+                                          len(self.spans), ctypes.byref(h)))
+        self._h = h
+        n, c, u = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        N.check(lib.slime_rs_batch_info(self._h, ctypes.byref(n), ctypes.byref(c), ctypes.byref(u)))
+        self.nobj, self.columns, self.units = int(n.value), int(c.value), int(u.value)
+
+    @classmethod
+    def packed(cls, lengths: Sequence[int], nshards: int, k: int, align: int = 64,
+               device: int = 0) -> tuple["Batch", int]:
+        """The usual layout: object o's nshards shards are its L_o rounded up to `align` elements
+        apart, and the objects follow each other; the same offsets serve src and dst.  Returns the
+        batch and the layout's total element count."""
+        if align < 1:
+            raise ValueError("align must be positive")
+        spans, off = [], 0
+        for L in lengths:
+            ss = -(-int(L) // align) * align
+            spans.append((off, ss, off, ss, int(L)))
+            off += nshards * ss
+        return cls(spans, k, device), off
+
+    def _check_extent(self, t: torch.Tensor, off: int, side: int, max_shard: int) -> None:
+        # Host-side bounds check of every span before launching a hand-written kernel.
+        key = (side, max_shard)
+        if key not in self._extents:
+            s = self.spans.astype(object)  # Python ints: no 64-bit wrap
+            live = [i for i in range(len(s)) if s[i, 4]]
+            ends = [(s[i, 2 * side] + max_shard * s[i, 2 * side + 1] + s[i, 4], i) for i in live]
+            self._extents[key] = max(ends) if ends else (0, -1)
+        last, o = self._extents[key]
+        if o >= 0 and (off < 0 or off + last > t.numel()):
+            raise ValueError(f"span {o} addresses element {off + last} of a {t.numel()}-element tensor")
+
+    def close(self) -> None:
+        if self._h:
+            lib.slime_rs_batch_destroy(self._h)  # waits for the device (hipFree)
             self._h = None
 
     def __del__(self):
