@@ -16,12 +16,13 @@ CACHETEST := tests/cpp/plan_cache_test
 COPYTEST := tests/cpp/copy_pool_test
 POOLTEST := tests/cpp/device_pool_test
 MFMATEST := tests/cpp/mfma_table_test
+FOLDTEST := tests/cpp/gfp_fold_test
 DMATEST  := tests/cpp/dma_plan_test
 REDOTEST := tests/cpp/redo_list_test
 RAGGEDTEST := tests/cpp/ragged_plan_test
 PROXYLOAD := tools/libproxy_load.so
 
-all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PROXYLOAD)
+all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PROXYLOAD)
 
 # Proxy-level load generator over the C-ABI (bench.py host_path.pooled): C++ threads, no GIL.
 $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(LIB)
@@ -43,6 +44,10 @@ $(DMATEST): tests/cpp/dma_plan_test.cpp $(SRC)/dma_plan.hpp
 # The matrix-core kernel's int8-limb arithmetic emulated on its table (mfma_table.hpp), CPU only.
 $(MFMATEST): tests/cpp/mfma_table_test.cpp $(SRC)/mfma_table.hpp $(SRC)/gfp.hpp $(SRC)/gfp_host.hpp
 	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/mfma_table_test.cpp
+
+# fold96 (gfp.hpp) against unsigned __int128 % p at the values that take its rare branches, CPU only.
+$(FOLDTEST): tests/cpp/gfp_fold_test.cpp $(SRC)/gfp.hpp $(SRC)/gfp_host.hpp
+	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/gfp_fold_test.cpp
 
 # Device routing of host calls (device_pool.hpp) with a fixed device count, CPU only.
 $(POOLTEST): tests/cpp/device_pool_test.cpp $(SRC)/device_pool.hpp $(SRC)/plan_cache.hpp
@@ -78,7 +83,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST)
+	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -102,6 +102,23 @@ def test_mfma_table_arithmetic_emulated():
     r = subprocess.run([MFMA_BIN], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "bit-exact" in r.stdout
+    assert "saturated cases at k=112, largest |D_e| = " in r.stdout
+
+
+FOLD_BIN = os.path.join(ROOT, "tests", "cpp", "gfp_fold_test")
+
+
+def test_fold96_against_int128_at_its_rare_branches():
+    """fold96 (gfp.hpp), the last step of every data kernel, compiled for the
+    host and compared with unsigned __int128 % p: V = q p + t and
+    q 2^32 + t - d around every limb boundary for hi = 0..300, the matrix-core
+    range (hi = 0, lo < 2^49), every (lo, hi) of edge limbs, 10^7 random
+    values.  The program itself refuses a value set that never takes
+    `u >> 32 == 1` or the final `w >= p`."""
+    subprocess.run(["make", "-C", ROOT, "tests/cpp/gfp_fold_test"], check=True, capture_output=True)
+    r = subprocess.run([FOLD_BIN], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "10000000 random bit-exact" in r.stdout
 
 
 DMA_BIN = os.path.join(ROOT, "tests", "cpp", "dma_plan_test")
