@@ -20,9 +20,10 @@ FOLDTEST := tests/cpp/gfp_fold_test
 DMATEST  := tests/cpp/dma_plan_test
 REDOTEST := tests/cpp/redo_list_test
 RAGGEDTEST := tests/cpp/ragged_plan_test
+PLANSETTEST := tests/cpp/planset_table_test
 PROXYLOAD := tools/libproxy_load.so
 
-all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PROXYLOAD)
+all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(PROXYLOAD)
 
 # Proxy-level load generator over the C-ABI (bench.py host_path.pooled): C++ threads, no GIL.
 $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(LIB)
@@ -32,6 +33,10 @@ $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(L
 # The ragged batch's host work tables (ragged_plan.hpp), CPU only.
 $(RAGGEDTEST): tests/cpp/ragged_plan_test.cpp $(SRC)/ragged_plan.hpp
 	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/ragged_plan_test.cpp
+
+# A plan set's host table and the planned batch tables (planset_table.hpp, ragged_plan.hpp), CPU only.
+$(PLANSETTEST): tests/cpp/planset_table_test.cpp $(SRC)/planset_table.hpp $(SRC)/ragged_plan.hpp
+	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/planset_table_test.cpp
 
 # The matrix-core redo list's counter protocol (redo_list.hpp) emulated with threads, CPU only.
 $(REDOTEST): tests/cpp/redo_list_test.cpp $(SRC)/redo_list.hpp
@@ -83,7 +88,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST)
+	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -297,10 +297,70 @@ int slime_rs_batch_destroy(slime_rs_batch_t batch);
  * slime_rs_plan_execute would take it); wider plans, and bases that are not
  * 4-byte aligned, run one column per lane (correct, not fast: there is no
  * matrix-core or k-template ragged kernel).  Also out of scope: ragged forms
- * of the byte-slot pipeline and of verify, and per-object plans (group the
- * objects by erasure pattern, one batch per group). */
+ * of the byte-slot pipeline and of verify.  A batch made by
+ * slime_rs_batch_create_planned is accepted too: its plan indices are ignored
+ * here, and its SLIME_RS_NO_PLAN objects are skipped. */
 int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
                                 void *stream);
+
+/* ---- plan sets: objects with different erasures repaired in one launch --------
+ * A plan set is a device-resident table of several plans with the same k.  A
+ * planned batch names one plan of a set per object, and ONE launch applies to
+ * every object its own plan: that plan's input shards, coefficient rows and
+ * output shards.  The plans of a set may have different row counts.  The use
+ * is a repair sweep: after a store dies every affected object misses a
+ * different shard, some more than one -- one reconstruct plan per distinct
+ * erasure pattern, one set, one launch. */
+typedef struct slime_rs_planset *slime_rs_planset_t;
+
+/* plan_of[o] for an intact object: no work, exactly like L == 0. */
+#define SLIME_RS_NO_PLAN UINT32_MAX
+/* Plans a set may hold (and the bound on a planned batch's nplans). */
+#define SLIME_RS_PLANSET_MAX_PLANS (1u << 20)
+
+/* A snapshot of nplans plans in one device table: each plan's rows, k, input
+ * indices, coefficient rows and its output indices as slime_rs_plan_set_outputs
+ * had set them at this moment.  Synchronous.  The member plans may be
+ * destroyed afterwards, and a later slime_rs_plan_set_outputs on one of them
+ * does not reach the set; creating a set does not mark them launched.  All
+ * plans must be on one device and share k.  SLIME_RS_ERR_INVALID_ARG: null
+ * arguments (or a null member), nplans == 0 or above
+ * SLIME_RS_PLANSET_MAX_PLANS, mixed k or device, a table of 16 GiB or more.
+ * The table takes 64 bytes per plan plus, per plan, its indices padded to 64
+ * bytes each and 64 * ceil(k / 16) bytes per row. */
+int slime_rs_planset_create(const slime_rs_plan_t *plans, uint32_t nplans, slime_rs_planset_t *set);
+/* Plans, k, the most rows of any plan and the highest input / output shard
+ * index over the set; any output may be NULL. */
+int slime_rs_planset_info(slime_rs_planset_t set, uint32_t *nplans, int *k, uint32_t *max_rows, uint32_t *in_max,
+                          uint32_t *out_max);
+/* As slime_rs_batch_destroy: hipFree waits for launches in flight; not inside
+ * a capture, and after the graphs that captured a launch of the set. */
+int slime_rs_planset_destroy(slime_rs_planset_t set);
+/* slime_rs_batch_create with a plan index per object: plan_of[o] < nplans (else
+ * SLIME_RS_ERR_INVALID_ARG, checked here on the host) is stored in object o's
+ * descriptor; plan_of[o] == SLIME_RS_NO_PLAN marks an intact object, which gets
+ * no work units and is neither read nor written, exactly like L == 0 (it does
+ * not count in slime_rs_batch_info's columns).  nplans is the plan count of the
+ * sets the batch will run with, 1..SLIME_RS_PLANSET_MAX_PLANS.  The batch stays
+ * usable with slime_rs_plan_execute_batch (see there). */
+int slime_rs_batch_create_planned(int device, int k, const slime_rs_span_t *spans, const uint32_t *plan_of,
+                                  uint32_t nplans, uint64_t nobj, slime_rs_batch_t *batch);
+/* For every span o of the batch with a plan, plan p = plan_of[o] of the set:
+ * out[o][out_idx_p[i]][b] = sum_j coeff_p[i][j] * in[o][in_idx_p[j]][b], b <
+ * L_o, in ONE launch; bit-identical to slime_rs_plan_execute run object by
+ * object with that object's plan.  Asynchronous, and capturable under exactly
+ * the rules of slime_rs_plan_execute_batch (static schedule inside captures at
+ * slime_rs_kernel_schedule 1, dynamic with a graph-held counter set at 2).
+ * The batch must be planned, and its nplans, k and device must equal the
+ * set's (SLIME_RS_ERR_INVALID_ARG).  dst == src with every plan's outputs set
+ * to its erased shards is the common call: each object is repaired in its own
+ * slots.  Forms as slime_rs_plan_execute_batch: k <= 16 over 4-byte aligned
+ * bases runs four columns a lane, anything else one column a lane.
+ * Out of scope: plan sets for the byte-slot pipeline and for verify,
+ * matrix-core or k-template planned kernels for wide codes, and sets mixing
+ * different k. */
+int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
+                                   void *stream);
 
 /* ==== fused byte-domain object pipeline (writeChunks / reconstruct on device) ====
  * Object slots: object o's slot starts at slots + o*slot_stride bytes and holds

@@ -45,6 +45,8 @@ class CacheStats(ctypes.Structure):
 
 
 ANY_DEVICE = -1
+NO_PLAN = 0xFFFFFFFF  # SLIME_RS_NO_PLAN: an intact object of a planned batch
+PLANSET_MAX_PLANS = 1 << 20
 
 
 class HostStats(ctypes.Structure):
@@ -126,6 +128,14 @@ SIGNATURES = [
     ("slime_rs_batch_info", ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p]),
     ("slime_rs_batch_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("slime_rs_plan_execute_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("slime_rs_planset_create", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("slime_rs_planset_info", ctypes.c_int, [ctypes.c_void_p, c_u32p, c_intp, c_u32p, c_u32p, c_u32p]),
+    ("slime_rs_planset_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("slime_rs_batch_create_planned", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+      ctypes.POINTER(ctypes.c_void_p)]),
+    ("slime_rs_planset_execute_batch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("slime_rs_verify_objects", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,

@@ -33,6 +33,7 @@ struct slime_rs_plan {
   uint32_t rows = 0, k = 0;
   uint32_t out_max = 0;               // highest destination shard index
   std::vector<uint32_t> in_idx_host;  // input shard indices (host copy, bounds checks)
+  std::vector<uint32_t> out_idx_host; // output shard indices as slime_rs_plan_set_outputs last left them
   std::vector<uint32_t> coeff;        // rows x k, host copy
   uint32_t* table = nullptr;          // device: coeff (rows x coeff_stride(k)) | in_idx (k) | out_idx (rows)
   const uint32_t* d_coeff = nullptr;
@@ -55,6 +56,18 @@ struct slime_rs_batch {
   slime::ragged::Desc* d_desc = nullptr;
   slime::ragged::Unit* d_units = nullptr;
   slime::ragged::Tail* d_tails = nullptr;
+  // slime_rs_batch_create_planned: the descriptors carry a plan index below nplans.
+  bool planned = false;
+  uint32_t nplans = 0;
+};
+
+// Several plans with the same k in one device table (slime_rs_planset_t;
+// planset_table.hpp): a snapshot, independent of the member plans.
+struct slime_rs_planset {
+  int device = 0;
+  uint32_t nplans = 0, k = 0;
+  uint32_t max_rows = 0, in_max = 0, out_max = 0;
+  uint32_t* d_table = nullptr;
 };
 
 namespace slime {

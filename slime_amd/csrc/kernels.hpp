@@ -315,6 +315,27 @@ struct RaggedLaunch {
 };
 hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t stream);
 
+// The same launch with a plan per object (slime_rs_planset_execute_batch):
+// desc[o] names plan desc[o].reserved[0] of the set whose device table
+// (planset_table.hpp) is `table`; that plan's inputs, rows and outputs are
+// applied to object o.  The batch was created planned, with the set's plan
+// count, so every index is below it.  Forms, schedules and capture rules are
+// launch_apply_ragged's.
+struct PlannedLaunch {
+  const uint32_t* in;
+  uint32_t* out;
+  const ragged::Desc* desc;
+  const ragged::Unit* units;
+  const ragged::Tail* tails;
+  uint32_t nunits;
+  uint64_t ntails;
+  int U, C;
+  const uint32_t* table;
+  uint32_t k;
+  bool vec_ok;
+};
+hipError_t launch_apply_planned(const PlannedLaunch& a, hipStream_t stream);
+
 // --- small host<->device transfers as one kernel (host_blit.hip) ----------
 // dst/src: device addresses (device memory, or pinned host memory mapped
 // into the device's address space); any alignment.

@@ -70,7 +70,7 @@ struct alignas(64) Desc {
   uint32_t nvec;                                    // whole 16-byte vectors per shard, L / 4
   uint32_t ntiles;                                  // ceil(nvec / 64 U)
   uint32_t ncols;                                   // L
-  uint32_t reserved[5];                             // zero (room for a plan index)
+  uint32_t reserved[5];                             // [0]: the object's plan index in a planned batch, else zero
 };
 static_assert(sizeof(Desc) == 64 && alignof(Desc) == 64, "one s_load_dwordx16 per descriptor");
 
@@ -102,6 +102,12 @@ SLIME_RAGGED_HD inline uint32_t ticket_entry(uint32_t l, uint32_t p, uint32_t nc
   return ((l >> 2) * nc + p) * 4 + (l & 3);
 }
 
+// A planned batch (slime_rs_batch_create_planned) names one plan of a plan set
+// (planset_table.hpp) per object: plan_of[o] < nplans goes into the
+// descriptor's first reserved word; kNoPlan marks an intact object, which
+// gets no units and no tails, exactly like L == 0.
+constexpr uint32_t kNoPlan = 0xFFFFFFFFu;
+
 struct Counts {
   uint64_t nobj = 0, columns = 0, tiles = 0, units = 0, tails = 0;
 };
@@ -112,7 +118,9 @@ inline uint64_t tails_of(uint64_t L) { return L & 3; }
 
 // Validates the spans and counts what build() would make, allocating nothing.
 // false: *why names the refusal.
-inline bool count(const Span* spans, uint64_t nobj, Geometry g, Counts* out, std::string* why) {
+// plan_of (optional): nobj plan indices below nplans, or kNoPlan.
+inline bool count(const Span* spans, uint64_t nobj, Geometry g, Counts* out, std::string* why,
+                  const uint32_t* plan_of = nullptr, uint32_t nplans = 0) {
   Counts c;
   c.nobj = nobj;
   if (nobj > 0xFFFFFFFFull) {
@@ -125,6 +133,14 @@ inline bool count(const Span* spans, uint64_t nobj, Geometry g, Counts* out, std
       *why = "span " + std::to_string(o) + ": L = " + std::to_string(L) +
              " is 2^30 or more (a ragged batch keeps shards under 4 GiB; use slime_rs_plan_execute)";
       return false;
+    }
+    if (plan_of) {
+      if (plan_of[o] == kNoPlan) continue;
+      if (plan_of[o] >= nplans) {
+        *why = "span " + std::to_string(o) + ": plan index " + std::to_string(plan_of[o]) + " of a set of " +
+               std::to_string(nplans);
+        return false;
+      }
     }
     c.columns += L;
     c.tiles += tiles_of(L, g.U);
@@ -147,8 +163,11 @@ struct Tables {
   std::vector<Tail> tails;
 };
 
-inline bool build(const Span* spans, uint64_t nobj, Geometry g, Tables* t, std::string* why) {
-  if (!count(spans, nobj, g, &t->counts, why)) return false;
+inline bool build(const Span* spans, uint64_t nobj, Geometry g, Tables* t, std::string* why,
+                  const uint32_t* plan_of = nullptr, uint32_t nplans = 0) {
+  if (!count(spans, nobj, g, &t->counts, why, plan_of, nplans)) return false;
+  // The columns of object o that the launch works on: none of an intact object.
+  auto len = [&](uint64_t o) { return plan_of && plan_of[o] == kNoPlan ? 0ull : spans[o].L; };
   t->g = g;
   t->desc.assign(nobj, Desc{});
   t->units.clear();
@@ -157,7 +176,7 @@ inline bool build(const Span* spans, uint64_t nobj, Geometry g, Tables* t, std::
   t->tails.reserve(t->counts.tails);
   // Segment length: whole ticket groups (4 units, 4 C tiles), the batch's groups over `segments`.
   uint64_t groups = 0;
-  for (uint64_t o = 0; o < nobj; ++o) groups += (units_of(spans[o].L, g) + 3) / 4;
+  for (uint64_t o = 0; o < nobj; ++o) groups += (units_of(len(o), g) + 3) / 4;
   const uint64_t nseg = g.segments ? g.segments : 1;
   const uint64_t seg_groups = groups > nseg ? (groups + nseg - 1) / nseg : 1;
   const uint64_t seg_tiles = seg_groups * 4 * (uint64_t)g.C;
@@ -167,17 +186,19 @@ inline bool build(const Span* spans, uint64_t nobj, Geometry g, Tables* t, std::
   std::vector<Seg> live;
   for (uint64_t o = 0; o < nobj; ++o) {
     const Span& s = spans[o];
+    const uint64_t L = len(o);
     Desc& d = t->desc[o];
     d.src_off = s.src_off;
     d.src_shard = s.src_shard_stride;
     d.dst_off = s.dst_off;
     d.dst_shard = s.dst_shard_stride;
-    d.nvec = (uint32_t)(s.L >> 2);
-    d.ntiles = (uint32_t)tiles_of(s.L, g.U);
-    d.ncols = (uint32_t)s.L;
+    d.nvec = (uint32_t)(L >> 2);
+    d.ntiles = (uint32_t)tiles_of(L, g.U);
+    d.ncols = (uint32_t)L;
+    d.reserved[0] = plan_of ? plan_of[o] : 0u;
     for (uint64_t t0 = 0; t0 < d.ntiles; t0 += seg_tiles)
       live.push_back(Seg{(uint32_t)o, (uint32_t)t0, (uint32_t)(t0 + seg_tiles < d.ntiles ? t0 + seg_tiles : d.ntiles)});
-    for (uint64_t b = (uint64_t)d.nvec << 2; b < s.L; ++b) t->tails.push_back(Tail{(uint32_t)o, (uint32_t)b});
+    for (uint64_t b = (uint64_t)d.nvec << 2; b < L; ++b) t->tails.push_back(Tail{(uint32_t)o, (uint32_t)b});
   }
   // Round after round over the segments that have units left, four units each.
   while (!live.empty()) {

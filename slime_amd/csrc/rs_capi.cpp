@@ -38,6 +38,7 @@
 #include "kernels.hpp"
 #include "mfma_table.hpp"
 #include "plan_cache.hpp"
+#include "planset_table.hpp"
 #include "rs_matrix.hpp"
 
 namespace slime {
@@ -149,6 +150,7 @@ int build_plan(int device, uint32_t rows, uint32_t k, const uint32_t* coeff, con
   plan->coeff.assign(coeff, coeff + (size_t)rows * k);
   plan->out_max = out_idx.empty() ? 0 : *std::max_element(out_idx.begin(), out_idx.end());
   plan->in_idx_host = in_idx;
+  plan->out_idx_host = out_idx;
   const uint32_t cs = coeff_stride(k);
   const size_t ncoef = (size_t)rows * cs;
   const size_t n_in = (k + 3) & ~3u, n_out = (rows + 3) & ~3u;
@@ -527,24 +529,28 @@ static hipError_t upload_table(const void* host, size_t bytes, void** dev) {
   return hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice);
 }
 
-int slime_rs_batch_create(int device, int k, const slime_rs_span_t* spans, uint64_t nobj, slime_rs_batch_t* batch) {
-  if (!batch) return fail(Status::InvalidArg, "batch_create: null batch");
+// Both batch constructors; plan_of == nullptr: an unplanned batch.
+static int create_batch(const std::string& what, int device, int k, const slime_rs_span_t* spans,
+                        const uint32_t* plan_of, uint32_t nplans, uint64_t nobj, slime_rs_batch_t* batch) {
+  if (!batch) return fail(Status::InvalidArg, what + ": null batch");
   *batch = nullptr;
-  if (k <= 0) return fail(Status::InvalidArg, "batch_create: k must be positive");
-  if (!spans && nobj) return fail(Status::InvalidArg, "batch_create: null spans");
+  if (k <= 0) return fail(Status::InvalidArg, what + ": k must be positive");
+  if (!spans && nobj) return fail(Status::InvalidArg, what + ": null spans");
   const ragged::Geometry g = ragged::geometry_for_k(k);
   const ragged::Span* sp = reinterpret_cast<const ragged::Span*>(spans);
   std::string why;
   ragged::Counts counts;
-  if (!ragged::count(sp, nobj, g, &counts, &why)) return fail(Status::InvalidArg, "batch_create: " + why);
+  if (!ragged::count(sp, nobj, g, &counts, &why, plan_of, nplans)) return fail(Status::InvalidArg, what + ": " + why);
   if (int rc = check_device(device)) return rc;
   ragged::Tables t;
-  if (!ragged::build(sp, nobj, g, &t, &why)) return fail(Status::InvalidArg, "batch_create: " + why);
+  if (!ragged::build(sp, nobj, g, &t, &why, plan_of, nplans)) return fail(Status::InvalidArg, what + ": " + why);
   auto b = std::make_unique<slime_rs_batch>();
   b->device = device;
   b->k = (uint32_t)k;
   b->g = g;
   b->counts = t.counts;
+  b->planned = plan_of != nullptr;
+  b->nplans = nplans;
   DeviceScope ds(device);
   hipError_t e = upload_table(t.desc.data(), t.desc.size() * sizeof(ragged::Desc), (void**)&b->d_desc);
   if (e == hipSuccess) e = upload_table(t.units.data(), t.units.size() * sizeof(ragged::Unit), (void**)&b->d_units);
@@ -553,10 +559,24 @@ int slime_rs_batch_create(int device, int k, const slime_rs_span_t* spans, uint6
   if (e == hipSuccess) e = warm_ticket_pool(device);
   if (e != hipSuccess) {
     free_batch_tables(b.get());
-    return fail_hip(e, "batch_create: work tables");
+    return fail_hip(e, (what + ": work tables").c_str());
   }
   *batch = b.release();
   return 0;
+}
+
+int slime_rs_batch_create(int device, int k, const slime_rs_span_t* spans, uint64_t nobj, slime_rs_batch_t* batch) {
+  return create_batch("batch_create", device, k, spans, nullptr, 0, nobj, batch);
+}
+
+int slime_rs_batch_create_planned(int device, int k, const slime_rs_span_t* spans, const uint32_t* plan_of,
+                                  uint32_t nplans, uint64_t nobj, slime_rs_batch_t* batch) {
+  if (batch) *batch = nullptr;
+  if (!plan_of && nobj) return fail(Status::InvalidArg, "batch_create_planned: null plan_of");
+  if (nplans == 0 || nplans > planset::kMaxPlans)
+    return fail(Status::InvalidArg, "batch_create_planned: nplans must be 1.." + std::to_string(planset::kMaxPlans));
+  static const uint32_t none = 0;  // nobj == 0: any non-null array marks the batch planned
+  return create_batch("batch_create_planned", device, k, spans, plan_of ? plan_of : &none, nplans, nobj, batch);
 }
 
 int slime_rs_batch_info(slime_rs_batch_t batch, uint64_t* nobj, uint64_t* columns, uint64_t* units) {
@@ -609,6 +629,104 @@ int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, co
   return 0;
 }
 
+// ---- plan sets (planset_table.hpp; the planned kernels of rs_ragged.hip) ----------
+
+int slime_rs_planset_create(const slime_rs_plan_t* plans, uint32_t nplans, slime_rs_planset_t* set) {
+  if (!set) return fail(Status::InvalidArg, "planset_create: null set");
+  *set = nullptr;
+  if (!plans) return fail(Status::InvalidArg, "planset_create: null plans");
+  if (nplans == 0) return fail(Status::InvalidArg, "planset_create: a plan set needs at least one plan");
+  for (uint32_t i = 0; i < nplans; ++i)
+    if (!plans[i]) return fail(Status::InvalidArg, "planset_create: plan " + std::to_string(i) + " is null");
+  const int device = plans[0]->device;
+  // The snapshot: each plan's indices as they stand now, its rows reduced as its own table holds them.
+  std::vector<std::vector<uint32_t>> coeff(nplans);
+  std::vector<planset::PlanView> views(nplans);
+  for (uint32_t i = 0; i < nplans; ++i) {
+    const slime_rs_plan* p = plans[i];
+    if (p->device != device)
+      return fail(Status::InvalidArg, "planset_create: plan " + std::to_string(i) + " is on device " +
+                                          std::to_string(p->device) + ", plan 0 on device " + std::to_string(device));
+    coeff[i].resize(p->coeff.size());
+    for (size_t q = 0; q < p->coeff.size(); ++q) coeff[i][q] = p->coeff[q] % kP;
+    views[i] = planset::PlanView{p->rows, p->k, p->in_idx_host.data(), p->out_idx_host.data(), coeff[i].data()};
+  }
+  planset::Table t;
+  std::string why;
+  if (!planset::build(views.data(), nplans, &t, &why)) return fail(Status::InvalidArg, "planset_create: " + why);
+  if (int rc = check_device(device)) return rc;
+  auto s = std::make_unique<slime_rs_planset>();
+  s->device = device;
+  s->nplans = t.nplans;
+  s->k = t.k;
+  s->max_rows = t.max_rows;
+  s->in_max = t.in_max;
+  s->out_max = t.out_max;
+  DeviceScope ds(device);
+  hipError_t e = upload_table(t.words.data(), t.words.size() * sizeof(uint32_t), (void**)&s->d_table);
+  if (e == hipSuccess) e = warm_ticket_pool(device);
+  if (e != hipSuccess) {
+    if (s->d_table) (void)hipFree(s->d_table);
+    return fail_hip(e, "planset_create: table");
+  }
+  *set = s.release();
+  return 0;
+}
+
+int slime_rs_planset_info(slime_rs_planset_t set, uint32_t* nplans, int* k, uint32_t* max_rows, uint32_t* in_max,
+                          uint32_t* out_max) {
+  if (!set) return fail(Status::InvalidArg, "planset_info: null set");
+  if (nplans) *nplans = set->nplans;
+  if (k) *k = (int)set->k;
+  if (max_rows) *max_rows = set->max_rows;
+  if (in_max) *in_max = set->in_max;
+  if (out_max) *out_max = set->out_max;
+  return 0;
+}
+
+int slime_rs_planset_destroy(slime_rs_planset_t set) {
+  if (!set) return fail(Status::InvalidArg, "planset_destroy: null set");
+  if (set->d_table) {
+    DeviceScope ds(set->device);
+    (void)hipFree(set->d_table);  // waits for the device: launches in flight have finished
+  }
+  delete set;
+  return 0;
+}
+
+int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
+                                   void* stream) {
+  if (!set) return fail(Status::InvalidArg, "planset_execute_batch: null set");
+  if (!batch) return fail(Status::InvalidArg, "planset_execute_batch: null batch");
+  if (!batch->planned)
+    return fail(Status::InvalidArg, "planset_execute_batch: the batch carries no plan indices "
+                                    "(create it with slime_rs_batch_create_planned)");
+  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
+    return fail(Status::InvalidArg, "planset_execute_batch: the batch was created for " + std::to_string(batch->nplans) +
+                                        " plans of k = " + std::to_string(batch->k) + " on device " +
+                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
+                                        " plans of k = " + std::to_string(set->k) + " on device " +
+                                        std::to_string(set->device));
+  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (!src || !dst) return fail(Status::InvalidArg, "planset_execute_batch: null buffer");
+  PlannedLaunch a;
+  a.in = src;
+  a.out = dst;
+  a.desc = batch->d_desc;
+  a.units = batch->d_units;
+  a.tails = batch->d_tails;
+  a.nunits = (uint32_t)batch->counts.units;
+  a.ntails = batch->counts.tails;
+  a.U = batch->g.U;
+  a.C = batch->g.C;
+  a.table = set->d_table;
+  a.k = set->k;
+  a.vec_ok = aligned4(src) && aligned4(dst);
+  DeviceScope ds(set->device);
+  HIP_TRY(launch_apply_planned(a, (hipStream_t)stream));
+  return 0;
+}
+
 // Shared by both verify entry points: the result arrays and the object count.
 static int check_verify_results(uint64_t nobj, const uint64_t* mismatches, const uint64_t* first, const char* what) {
   if (nobj > 0xFFFFFFFFull) return fail(Status::InvalidArg, std::string(what) + ": nobj exceeds 2^32-1");
@@ -652,6 +770,7 @@ int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
   HIP_TRY(hipMemcpy(const_cast<uint32_t*>(plan->d_out_idx), idx.data(), idx.size() * sizeof(uint32_t),
                     hipMemcpyHostToDevice));
   plan->out_max = *std::max_element(idx.begin(), idx.end());
+  plan->out_idx_host = idx;
   return 0;
 }
 

@@ -38,9 +38,15 @@
 // Columns past each object's last whole vector (L % 4; all of an object of
 // fewer than 4 columns) are {object, column} items strided over the grid
 // after the walk, one per lane, through apply_column<K>.
+//
+// Plan sets (slime_rs_planset_execute_batch): rs_apply_planned_kernel and
+// rs_apply_planned_column_kernel below are the twins of the two kernels with a
+// plan PER OBJECT, named by the object's descriptor and read from a plan set's
+// table (planset_table.hpp).  The single-plan kernels are unchanged.
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "planset_table.hpp"
 #include "rs_apply_kernel.hpp"
 
 namespace slime {
@@ -299,6 +305,150 @@ __global__ __launch_bounds__(kBlock) void rs_apply_ragged_column_kernel(
   ragged_tails<0>(in, out, descs, tails, ntails, coeff, in_idx, out_idx, rows, k);
 }
 
+// ---- plan sets: every object its own plan (slime_rs_planset_execute_batch) ----
+// The planned twins of the two kernels above.  The batch's descriptors carry a
+// plan index (Desc::reserved[0]); `tab` is the set's table (planset_table.hpp):
+// the 64-byte record of plan i at word 16 i gives the plan's row count and the
+// word offsets of its input indices, output indices and coefficient rows, each
+// padded as the row-load idioms above expect.  On entering a unit of another
+// object the wave takes, after the descriptor, its plan index, the plan's
+// record (one scalar load each) and its input indices (one s_load_dwordx16), and recomputes the K
+// input bases from them.
+//
+// The software pipeline keeps two tiles live, the one being stored and the
+// one being loaded, and after advance() they may belong to objects with
+// different plans: a PlannedTileOut therefore carries its OWN tile's
+// coefficient and output-index offsets and row count, fixed when the tile's
+// loads are issued, and the store of the earlier tile never reads the walk's
+// current plan (`pl`).
+
+// A plan record's live fields in SGPRs.
+struct PlanRef {
+  uint32_t rows, in_off, out_off, coeff_off;
+};
+// The record of object obj's plan: the index from the descriptor's line (which
+// the walk has just loaded; ObjRef and load_desc stay as the single-plan
+// kernels compile them), then the record, two dependent scalar loads.
+__device__ __forceinline__ PlanRef load_plan(const uint32_t* __restrict__ tab, const Desc* __restrict__ descs,
+                                             uint32_t obj) {
+  const uint32_t plan = descs[obj].reserved[0];
+  const apply::u32x4 v = *reinterpret_cast<const apply::u32x4*>(tab + (uint64_t)plan * planset::kRecordWords);
+  return PlanRef{v[0], v[1], v[2], v[3]};
+}
+
+struct PlannedTileOut {
+  uint32_t* ob;
+  uint64_t shard;
+  uint32_t nvec, g0;
+  uint32_t coeff_off, out_off, rows;  // the tile's own plan
+};
+
+// ragged_tails with each item's plan read through its descriptor.
+template <int K>
+__device__ __forceinline__ void planned_tails(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                              const Desc* __restrict__ descs, const Tail* __restrict__ tails,
+                                              uint64_t ntails, const uint32_t* __restrict__ tab, uint32_t k) {
+  const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint64_t nthr = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t t = tid; t < ntails; t += nthr) {
+    const Tail it = tails[t];
+    const Desc* const d = descs + it.obj;
+    const uint32_t* const r = tab + (uint64_t)d->reserved[0] * planset::kRecordWords;
+    apply::apply_column<K>(in + d->src_off, out + d->dst_off, tab + r[3], tab + r[1], d->src_shard, tab + r[2],
+                           d->dst_shard, r[0], k, (uint64_t)it.col);
+  }
+}
+
+template <int K, int U, int C, int NC, bool NTL, bool NTS, bool DYN, bool PIPE>
+__global__ __launch_bounds__(kBlock) void rs_apply_planned_kernel(
+    const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const Desc* __restrict__ descs,
+    const Unit* __restrict__ units, const Tail* __restrict__ tails, const uint32_t* __restrict__ tab, uint32_t nunits,
+    uint64_t ntails, uint32_t k, uint32_t* __restrict__ ticket) {
+  static_assert(K > 0 && K <= 16 && NC > 0 && NC <= 64, "compile-time k only");
+  static_assert(PIPE || !DYN, "the dynamic walk is double-buffered");
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  UnitWalk<C, NC, DYN> w(ticket, units, descs, nunits, lane, wave, gridDim.x * kWaves);
+  const uint32_t* sb[K];
+  PlanRef pl{};  // the plan of the walk's current object
+  auto bases = [&]() {
+    pl = load_plan(tab, descs, w.obj);
+    const u32x16 idx = *reinterpret_cast<const u32x16*>(tab + pl.in_off);  // K <= 16: one line
+#pragma unroll
+    for (int j = 0; j < K; ++j) sb[j] = in + w.d.src_off + (uint64_t)idx[j] * w.d.src_shard;
+  };
+  auto here = [&]() {
+    return PlannedTileOut{out + w.d.dst_off, w.d.dst_shard, w.d.nvec, w.tile() * (64 * U) + lane,
+                          pl.coeff_off,      pl.out_off,    pl.rows};
+  };
+  auto store = [&](const uint4(&x)[U][K], const PlannedTileOut& t) {
+    apply::store_tile<K, U, NTS>(x, t.ob, tab + t.coeff_off, tab + t.out_off, t.shard, t.rows, t.g0, t.nvec);
+  };
+  if constexpr (PIPE) {
+    if (w.live) {
+      uint4 xa[U][K], xb[U][K];
+      bases();
+      PlannedTileOut ta = here(), tb = ta;
+      apply::load_tile<K, U, NTL>(xa, sb, ta.g0, ta.nvec);
+      for (;;) {
+        w.advance();
+        // Past the last unit the prefetch re-reads the current tile (unconditional loads, see load_tile).
+        tb = ta;
+        if (w.live) {
+          if (w.fresh) bases();
+          tb = here();
+        }
+        apply::load_tile<K, U, NTL>(xb, sb, tb.g0, tb.nvec);
+        store(xa, ta);  // ta's own plan: bases() may just have moved `pl` on to tb's
+        if (!w.live) break;
+        w.advance();
+        ta = tb;
+        if (w.live) {
+          if (w.fresh) bases();
+          ta = here();
+        }
+        apply::load_tile<K, U, NTL>(xa, sb, ta.g0, ta.nvec);
+        store(xb, tb);
+        if (!w.live) break;
+      }
+    }
+  } else {
+    while (w.live) {
+      uint4 x[U][K];
+      if (w.fresh) bases();
+      const PlannedTileOut t = here();
+      apply::load_tile<K, U, NTL>(x, sb, t.g0, t.nvec);
+      store(x, t);
+      w.advance();
+    }
+  }
+  w.finish();
+  planned_tails<K>(in, out, descs, tails, ntails, tab, k);
+}
+
+// One column per lane over the same unit list (static walk), each unit with
+// its object's plan: generic k through wide_dot, any alignment.
+__global__ __launch_bounds__(kBlock) void rs_apply_planned_column_kernel(
+    const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const Desc* __restrict__ descs,
+    const Unit* __restrict__ units, const Tail* __restrict__ tails, const uint32_t* __restrict__ tab, uint32_t nunits,
+    uint64_t ntails, uint32_t k, uint32_t tile_cols, uint32_t unit_tiles) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t nwaves = gridDim.x * kWaves;
+  for (uint64_t e = wave; e < nunits; e += nwaves) {
+    const Unit u = units[e];
+    const ObjRef d = load_desc(descs, u.obj);
+    const PlanRef pl = load_plan(tab, descs, u.obj);
+    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
+    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)d.nvec << 2;
+    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+    for (uint64_t b = b0 + lane; b < b1; b += 64)
+      apply::apply_column<0>(in + d.src_off, out + d.dst_off, tab + pl.coeff_off, tab + pl.in_off, d.src_shard,
+                             tab + pl.out_off, d.dst_shard, pl.rows, k, b);
+  }
+  planned_tails<0>(in, out, descs, tails, ntails, tab, k);
+}
+
 }  // namespace ragged
 
 namespace {
@@ -310,7 +460,8 @@ constexpr uint64_t kQueueBlocks = 256;  // one block per CU, as launch_queue (rs
 
 // Blocks of a ragged launch: one wave per unit up to `full` (queue_blocks),
 // and enough lanes for the tail items of a batch of many short objects.
-uint64_t ragged_blocks(uint64_t full, const RaggedLaunch& a) {
+template <class Launch>  // RaggedLaunch or PlannedLaunch
+uint64_t ragged_blocks(uint64_t full, const Launch& a) {
   const uint64_t by_units = queue_blocks(full, a.nunits);
   const uint64_t by_tails = (a.ntails + kBlock - 1) / kBlock;
   const uint64_t want = by_tails < full ? by_tails : full;
@@ -361,6 +512,48 @@ hipError_t launch_columns(const RaggedLaunch& a, hipStream_t s) {
 
 #undef SLIME_RAGGED_ARGS
 
+// The planned launches: the same grids and the same choice between the
+// schedules as the single-plan launches above.
+#define SLIME_PLANNED_ARGS(a) (a).in, (a).out, (a).desc, (a).units, (a).tails, (a).table, (a).nunits, (a).ntails, (a).k
+
+template <int K, bool PIPE>
+hipError_t launch_planned_static(const PlannedLaunch& a, hipStream_t s) {
+  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
+  const uint64_t blocks = ragged_blocks(K <= 12 ? 256 : 1024, a);
+  hipLaunchKernelGGL((ragged::rs_apply_planned_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, false, PIPE>),
+                     dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_PLANNED_ARGS(a), nullptr);
+  return hipGetLastError();
+}
+
+template <int K>
+hipError_t dispatch_planned(const PlannedLaunch& a, hipStream_t s) {
+  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
+  if (!pipelined_kernels()) return launch_planned_static<K, false>(a, s);
+  if (queue_allowed(s) && a.nunits > tiny_queue_units()) {
+    bool launched = false;
+    const uint64_t blocks = ragged_blocks(kQueueBlocks, a);
+    const hipError_t e = with_tickets(
+        s,
+        [&](uint32_t* set) {
+          hipLaunchKernelGGL((ragged::rs_apply_planned_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, true, true>),
+                             dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_PLANNED_ARGS(a), set);
+          return hipGetLastError();
+        },
+        &launched);
+    if (launched || e != hipSuccess) return e;
+  }
+  return launch_planned_static<K, true>(a, s);
+}
+
+hipError_t launch_planned_columns(const PlannedLaunch& a, hipStream_t s) {
+  const uint64_t blocks = ragged_blocks(1024, a);
+  hipLaunchKernelGGL(ragged::rs_apply_planned_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                     SLIME_PLANNED_ARGS(a), 256u * (uint32_t)a.U, (uint32_t)a.C);
+  return hipGetLastError();
+}
+
+#undef SLIME_PLANNED_ARGS
+
 }  // namespace
 
 hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t s) {
@@ -386,6 +579,31 @@ hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t s) {
     case 14: return dispatch<14>(a, s);
     case 15: return dispatch<15>(a, s);
     default: return dispatch<16>(a, s);
+  }
+}
+
+hipError_t launch_apply_planned(const PlannedLaunch& a, hipStream_t s) {
+  (void)hipGetLastError();  // report only this launch's error, not one left on the thread
+  if (a.nunits == 0 && a.ntails == 0) return hipSuccess;
+  if (a.k > 16 || !a.vec_ok) return launch_planned_columns(a, s);
+  if (a.U != ragged::unroll_for_k((int)a.k) || a.C != ragged::unit_tiles_for_k((int)a.k)) return hipErrorInvalidValue;
+  switch (a.k) {
+    case 1: return dispatch_planned<1>(a, s);
+    case 2: return dispatch_planned<2>(a, s);
+    case 3: return dispatch_planned<3>(a, s);
+    case 4: return dispatch_planned<4>(a, s);
+    case 5: return dispatch_planned<5>(a, s);
+    case 6: return dispatch_planned<6>(a, s);
+    case 7: return dispatch_planned<7>(a, s);
+    case 8: return dispatch_planned<8>(a, s);
+    case 9: return dispatch_planned<9>(a, s);
+    case 10: return dispatch_planned<10>(a, s);
+    case 11: return dispatch_planned<11>(a, s);
+    case 12: return dispatch_planned<12>(a, s);
+    case 13: return dispatch_planned<13>(a, s);
+    case 14: return dispatch_planned<14>(a, s);
+    case 15: return dispatch_planned<15>(a, s);
+    default: return dispatch_planned<16>(a, s);
   }
 }
 

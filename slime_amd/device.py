@@ -304,16 +304,37 @@ class Batch:
     encode plan and every reconstruct plan of a code (Plan.execute_batch).
 
     spans: one (src_off, src_shard_stride, dst_off, dst_shard_stride, L) per object, in uint32
-    elements; L < 2**30, L == 0 is skipped."""
+    elements; L < 2**30, L == 0 is skipped.
 
-    def __init__(self, spans, k: int, device: int = 0):
+    plans, nplans: a planned batch for PlanSet.execute_batch -- plans[o] < nplans is object o's plan
+    of the set, N.NO_PLAN (2**32 - 1) an intact object, skipped like L == 0.  Plan.execute_batch
+    accepts a planned batch too and ignores the indices."""
+
+    def __init__(self, spans, k: int, device: int = 0, plans=None, nplans: Optional[int] = None):
         self._h = None
         self.spans = np.ascontiguousarray(np.asarray(spans, dtype=np.uint64).reshape(-1, 5))
         self.k, self.device = int(k), int(device)
         self._extents: dict = {}
+        self.plans, self.nplans = None, None
         h = ctypes.c_void_p()
-        N.check(lib.slime_rs_batch_create(self.device, self.k, self.spans.ctypes.data if len(self.spans) else None,
-                                          len(self.spans), ctypes.byref(h)))
+        sp = self.spans.ctypes.data if len(self.spans) else None
+        if plans is None:
+            if nplans is not None:
+                raise ValueError("nplans needs the per-object plan indices (plans=...)")
+            N.check(lib.slime_rs_batch_create(self.device, self.k, sp, len(self.spans), ctypes.byref(h)))
+        else:
+            # A planned batch (slime_rs_batch_create_planned): plans[o] names object o's plan of a
+            # PlanSet with nplans plans, N.NO_PLAN an intact object that the launch leaves alone.
+            pl = np.asarray(plans)
+            if pl.shape != (len(self.spans),) or (len(pl) and (pl.min() < 0 or pl.max() > N.NO_PLAN)):
+                raise ValueError("plans needs one index in [0, 2**32) per span")
+            if nplans is None:
+                raise ValueError("a planned batch needs nplans, the plan count of its PlanSet")
+            self.plans = np.ascontiguousarray(pl.astype(np.uint32))
+            self.nplans = int(nplans)
+            N.check(lib.slime_rs_batch_create_planned(self.device, self.k, sp,
+                                                      self.plans.ctypes.data if len(self.plans) else None,
+                                                      self.nplans, len(self.spans), ctypes.byref(h)))
         self._h = h
         n, c, u = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         N.check(lib.slime_rs_batch_info(self._h, ctypes.byref(n), ctypes.byref(c), ctypes.byref(u)))
@@ -321,10 +342,10 @@ class Batch:
 
     @classmethod
     def packed(cls, lengths: Sequence[int], nshards: int, k: int, align: int = 64,
-               device: int = 0) -> tuple["Batch", int]:
+               device: int = 0, plans=None, nplans: Optional[int] = None) -> tuple["Batch", int]:
         """The usual layout: object o's nshards shards are its L_o rounded up to `align` elements
         apart, and the objects follow each other; the same offsets serve src and dst.  Returns the
-        batch and the layout's total element count."""
+        batch and the layout's total element count.  plans / nplans: a planned batch (see Batch)."""
         if align < 1:
             raise ValueError("align must be positive")
         spans, off = [], 0
@@ -332,14 +353,17 @@ class Batch:
             ss = -(-int(L) // align) * align
             spans.append((off, ss, off, ss, int(L)))
             off += nshards * ss
-        return cls(spans, k, device), off
+        if plans is None and nplans is None:
+            return cls(spans, k, device), off
+        return cls(spans, k, device, plans=plans, nplans=nplans), off
 
     def _check_extent(self, t: torch.Tensor, off: int, side: int, max_shard: int) -> None:
         # Host-side bounds check of every span before launching a hand-written kernel.
         key = (side, max_shard)
         if key not in self._extents:
             s = self.spans.astype(object)  # Python ints: no 64-bit wrap
-            live = [i for i in range(len(s)) if s[i, 4]]
+            plans = getattr(self, "plans", None)  # a planned batch's intact objects address nothing
+            live = [i for i in range(len(s)) if s[i, 4] and (plans is None or plans[i] != N.NO_PLAN)]
             ends = [(s[i, 2 * side] + max_shard * s[i, 2 * side + 1] + s[i, 4], i) for i in live]
             self._extents[key] = max(ends) if ends else (0, -1)
         last, o = self._extents[key]
@@ -349,6 +373,90 @@ class Batch:
     def close(self) -> None:
         if self._h:
             lib.slime_rs_batch_destroy(self._h)  # waits for the device (hipFree)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
+class PlanSet:
+    """Several plans with the same k in one device table (slime_rs_planset_t): with a planned
+    Batch, one launch applies to every object its own plan -- a repair sweep over objects that
+    miss different shards.  A snapshot: the plans may be closed afterwards."""
+
+    def __init__(self, plans: Sequence[Plan]):
+        self._h = None
+        plans = list(plans)
+        if not plans:
+            raise ValueError("a plan set needs at least one plan")
+        hv = (ctypes.c_void_p * len(plans))(*[p._h for p in plans])
+        h = ctypes.c_void_p()
+        N.check(lib.slime_rs_planset_create(hv, len(plans), ctypes.byref(h)))
+        self._h = h
+        self.device = plans[0].device
+        n, k = ctypes.c_uint32(), ctypes.c_int()
+        r, i, o = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        N.check(lib.slime_rs_planset_info(self._h, ctypes.byref(n), ctypes.byref(k), ctypes.byref(r),
+                                          ctypes.byref(i), ctypes.byref(o)))
+        self.nplans, self.k, self.max_rows, self.in_max, self.out_max = n.value, k.value, r.value, i.value, o.value
+
+    @classmethod
+    def for_erasures(cls, need: int, total: int, patterns, device: int = 0) -> tuple["PlanSet", np.ndarray]:
+        """One in-place reconstruct plan per DISTINCT erasure pattern: patterns[o] lists object o's
+        erased shard indices (empty or None: intact).  Each plan reads the first `need` survivors in
+        index order and writes the erased shards back into their own slots.  Returns the set and the
+        per-object plan indices (uint32, N.NO_PLAN for intact objects) for Batch(..., plans=...)."""
+        index: dict = {}
+        plan_of = np.full(len(patterns), N.NO_PLAN, dtype=np.uint32)
+        for o, pat in enumerate(patterns):
+            key = tuple(sorted(set(int(x) for x in pat))) if pat is not None else ()
+            if not key:
+                continue
+            if key[0] < 0 or key[-1] >= total or total - len(key) < need:
+                raise ValueError(f"object {o}: erasures {key} leave fewer than {need} of {total} shards")
+            plan_of[o] = index.setdefault(key, len(index))
+        if not index:
+            raise ValueError("no object has an erasure: nothing to repair")
+        plans = []
+        try:
+            for key in index:  # insertion order: plan i is pattern i
+                have = [i for i in range(total) if i not in key][:need]
+                plans.append(Plan.reconstruct(need, total, have, list(key), device).set_outputs(list(key)))
+            return cls(plans), plan_of
+        finally:
+            for p in plans:
+                p.close()
+
+    def execute_batch(self, src: torch.Tensor, dst: torch.Tensor, batch: Batch,
+                      stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0, dst_offset: int = 0) -> None:
+        """One launch over a planned batch (slime_rs_planset_execute_batch): every object with its
+        own plan of the set.  dst may be src (each object repaired in its own slots).  Asynchronous."""
+        for t in (src, dst):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan set's device")
+        if getattr(batch, "plans", None) is None:
+            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
+        if batch.device != self.device or batch.k != self.k or batch.nplans != self.nplans:
+            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
+                             f"the set has {self.nplans} plans of k={self.k} on device {self.device}")
+        # The set-wide highest shard indices: every object is checked as if it ran the widest plan.
+        batch._check_extent(src, src_offset, 0, self.in_max)
+        batch._check_extent(dst, dst_offset, 1, self.out_max)
+        _note_unprobed(src)
+        if dst.data_ptr() != src.data_ptr():
+            _note_unprobed(dst)
+        N.check(lib.slime_rs_planset_execute_batch(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                                                   ctypes.c_void_p(dst.data_ptr() + 4 * dst_offset),
+                                                   _stream_handle(self.device, stream)))
+
+    def close(self) -> None:
+        if self._h:
+            lib.slime_rs_planset_destroy(self._h)  # waits for the device (hipFree)
             self._h = None
 
     def __del__(self):
