@@ -8,7 +8,7 @@ SRC      := slime_amd/csrc
 OBJ      := build/obj
 LIB      := slime_amd/lib/libslime_rs.so
 
-OBJS := $(OBJ)/rs_apply.o $(OBJ)/rs_apply_k32.o $(OBJ)/rs_apply_mfma.o $(OBJ)/rs_verify.o $(OBJ)/rs_ragged.o $(OBJ)/rs_bytes.o $(OBJ)/rs_bytes_k32.o $(OBJ)/rs_bytes_mfma.o $(OBJ)/gf_codec.o $(OBJ)/host_blit.o $(OBJ)/rs_matrix.o $(OBJ)/host_copy.o $(OBJ)/host_codec.o $(OBJ)/digest.o $(OBJ)/device_alloc.o $(OBJ)/host_pipeline.o $(OBJ)/go_api.o $(OBJ)/object_calls.o $(OBJ)/rs_capi.o
+OBJS := $(OBJ)/rs_apply.o $(OBJ)/rs_apply_k32.o $(OBJ)/rs_apply_mfma.o $(OBJ)/rs_verify.o $(OBJ)/rs_ragged.o $(OBJ)/rs_verify_ragged.o $(OBJ)/rs_bytes.o $(OBJ)/rs_bytes_k32.o $(OBJ)/rs_bytes_mfma.o $(OBJ)/gf_codec.o $(OBJ)/host_blit.o $(OBJ)/rs_matrix.o $(OBJ)/host_copy.o $(OBJ)/host_codec.o $(OBJ)/digest.o $(OBJ)/device_alloc.o $(OBJ)/host_pipeline.o $(OBJ)/go_api.o $(OBJ)/object_calls.o $(OBJ)/rs_capi.o
 HDRS := $(wildcard $(SRC)/*.hpp) include/slime_rs.h
 
 CXXTEST  := tests/cpp/rs_host_test
@@ -21,9 +21,10 @@ DMATEST  := tests/cpp/dma_plan_test
 REDOTEST := tests/cpp/redo_list_test
 RAGGEDTEST := tests/cpp/ragged_plan_test
 PLANSETTEST := tests/cpp/planset_table_test
+STEPTEST := tests/cpp/verify_step_test
 PROXYLOAD := tools/libproxy_load.so
 
-all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(PROXYLOAD)
+all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROXYLOAD)
 
 # Proxy-level load generator over the C-ABI (bench.py host_path.pooled): C++ threads, no GIL.
 $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(LIB)
@@ -33,6 +34,10 @@ $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(L
 # The ragged batch's host work tables (ragged_plan.hpp), CPU only.
 $(RAGGEDTEST): tests/cpp/ragged_plan_test.cpp $(SRC)/ragged_plan.hpp
 	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/ragged_plan_test.cpp
+
+# The ragged verify's step rule (verify_step.hpp) over every batch tile, CPU only.
+$(STEPTEST): tests/cpp/verify_step_test.cpp $(SRC)/verify_step.hpp $(SRC)/ragged_plan.hpp
+	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/verify_step_test.cpp
 
 # A plan set's host table and the planned batch tables (planset_table.hpp, ragged_plan.hpp), CPU only.
 $(PLANSETTEST): tests/cpp/planset_table_test.cpp $(SRC)/planset_table.hpp $(SRC)/ragged_plan.hpp
@@ -88,7 +93,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST)
+	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

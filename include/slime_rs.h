@@ -297,7 +297,7 @@ int slime_rs_batch_destroy(slime_rs_batch_t batch);
  * slime_rs_plan_execute would take it); wider plans, and bases that are not
  * 4-byte aligned, run one column per lane (correct, not fast: there is no
  * matrix-core or k-template ragged kernel).  Also out of scope: ragged forms
- * of the byte-slot pipeline and of verify.  A batch made by
+ * of the byte-slot pipeline.  A batch made by
  * slime_rs_batch_create_planned is accepted too: its plan indices are ignored
  * here, and its SLIME_RS_NO_PLAN objects are skipped. */
 int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
@@ -356,11 +356,44 @@ int slime_rs_batch_create_planned(int device, int k, const slime_rs_span_t *span
  * to its erased shards is the common call: each object is repaired in its own
  * slots.  Forms as slime_rs_plan_execute_batch: k <= 16 over 4-byte aligned
  * bases runs four columns a lane, anything else one column a lane.
- * Out of scope: plan sets for the byte-slot pipeline and for verify,
+ * Out of scope: plan sets for the byte-slot pipeline,
  * matrix-core or k-template planned kernels for wide codes, and sets mixing
  * different k. */
 int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
                                    void *stream);
+
+/* ---- ragged verify: scrub objects of different lengths in one launch ----------
+ * slime_rs_plan_verify asked of every span of a batch, in ONE launch: inputs
+ * are read at src + src_off + in_idx[j]*src_shard_stride, stored rows at cmp +
+ * dst_off + out_idx[i]*dst_shard_stride (cmp may be src), L_o columns each.  A
+ * column mismatches iff the canonical residue is not bit-identical to the
+ * stored word (a stored p+3 where 3 is computed counts); inputs may be any
+ * uint32.
+ * Results: two device arrays of nobj x rows uint64, row-major [o][i] -- for the
+ * set form nobj x max_rows, max_rows as slime_rs_planset_info reports it.
+ * first[o][i] is a column inside object o, 0 .. L_o-1, or UINT64_MAX.  The call
+ * initialises both arrays on the stream whenever nobj > 0 (one kernel node,
+ * as slime_rs_plan_verify); entries of objects with L == 0, of
+ * SLIME_RS_NO_PLAN objects and, in the set form, of rows at or past an object's
+ * own plan's row count keep the initial values (0, UINT64_MAX).  An empty
+ * batch launches nothing but the initialisation.
+ * Nothing but the two result arrays is written and no scratch is used.
+ * Asynchronous, and capturable under exactly the rules of
+ * slime_rs_plan_execute_batch; plans or sets of more than 64 rows run in row
+ * blocks of 64, one launch (and one counter set) each.  The single-plan form
+ * marks the plan as launched and accepts a planned batch (plan indices
+ * ignored, SLIME_RS_NO_PLAN objects skipped); the set form marks nothing.
+ * SLIME_RS_ERR_INVALID_ARG: null arguments, a plan or set whose k or device is
+ * not the batch's, and for the set form an unplanned batch or one whose nplans
+ * differs from the set's.
+ * Forms: k <= 16 over 4-byte aligned src and cmp runs four columns a lane,
+ * anything else one column a lane (correct, not fast).  Out of scope:
+ * matrix-core or k-template ragged verify for wide codes, ragged or planned
+ * forms of slime_rs_verify_objects, locating which shard is wrong. */
+int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
+                               const uint32_t *cmp, uint64_t *mismatches, uint64_t *first, void *stream);
+int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src,
+                                  const uint32_t *cmp, uint64_t *mismatches, uint64_t *first, void *stream);
 
 /* ==== fused byte-domain object pipeline (writeChunks / reconstruct on device) ====
  * Object slots: object o's slot starts at slots + o*slot_stride bytes and holds

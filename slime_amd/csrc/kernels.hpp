@@ -336,6 +336,46 @@ struct PlannedLaunch {
 };
 hipError_t launch_apply_planned(const PlannedLaunch& a, hipStream_t stream);
 
+// --- ragged verify (rs_verify_ragged.hip) -------------------------------------
+// launch_verify's question asked of a ragged batch: for every object o and row
+// i, mismatches[o*rows + i] = the columns b < L_o whose stored word at
+// cmp + dst_off + out_idx[i]*dst_shard + b differs from the canonical residue
+// of row i over the inputs at in + src_off + in_idx[j]*src_shard + b, and
+// first[o*rows + i] = the lowest such column inside the object or UINT64_MAX.
+// Offsets and strides are the descriptors' (uint32 elements).
+//   table == nullptr: one plan (coeff / in_idx / out_idx, `rows` rows) for
+//     every object of the batch;
+//   table != nullptr: a plan set's table, object o checked against plan
+//     desc[o].reserved[0]; `rows` is the set's max_rows (the result arrays' row
+//     stride), rows at or past an object's own plan's keep their initial values.
+// The launch initialises both result arrays (nobj x rows) on the stream with
+// rs_verify_init_kernel whenever nobj > 0, writes nothing else and uses no
+// scratch.  Forms, schedules and capture rules are launch_apply_ragged's; more
+// than 64 rows go in row blocks of 64, one launch (and counter set) each.
+struct RaggedVerifyLaunch {
+  const uint32_t* in;
+  const uint32_t* cmp;
+  const ragged::Desc* desc;
+  const ragged::Unit* units;
+  const ragged::Tail* tails;
+  uint32_t nunits;
+  uint64_t ntails;
+  int U, C;
+  const uint32_t* coeff = nullptr;
+  const uint32_t* in_idx = nullptr;
+  const uint32_t* out_idx = nullptr;
+  const uint32_t* table = nullptr;
+  uint64_t* mismatches;
+  uint64_t* first;
+  uint64_t nobj;
+  uint32_t rows, k;
+  bool vec_ok;
+};
+hipError_t launch_verify_ragged(const RaggedVerifyLaunch& v, hipStream_t stream);
+// The result arrays' initial state (count 0, first UINT64_MAX) for n entries:
+// rs_verify_init_kernel on the stream, a kernel node in a capture (rs_verify.hip).
+hipError_t launch_verify_init(uint64_t* mismatches, uint64_t* first, uint64_t n, hipStream_t stream);
+
 // --- small host<->device transfers as one kernel (host_blit.hip) ----------
 // dst/src: device addresses (device memory, or pinned host memory mapped
 // into the device's address space); any alignment.

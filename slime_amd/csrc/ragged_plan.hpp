@@ -83,7 +83,7 @@ struct Tail {
 static_assert(sizeof(Unit) == 8 && sizeof(Tail) == 8, "8-byte list entries");
 
 // The dynamic walk's dealing of the unit list over NC ticket counters
-// (UnitWalk, rs_ragged.hip; TicketWalk's, rs_apply_kernel.hpp): the list is
+// (UnitWalk, rs_ragged_walk.hpp; TicketWalk's, rs_apply_kernel.hpp): the list is
 // cut into groups of four consecutive entries, group g belongs to partition
 // g % NC, and ticket l of partition p is entry l % 4 of the partition's
 // (l / 4)-th group.  A partition hands out 4 tickets per group it owns; the

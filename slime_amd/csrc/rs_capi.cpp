@@ -754,6 +754,76 @@ int slime_rs_plan_verify(slime_rs_plan_t plan, const uint32_t* src, slime_rs_lay
   return 0;
 }
 
+// ---- ragged verify (rs_verify_ragged.hip) ------------------------------------------
+
+// The batch's side of a ragged verify launch.
+static RaggedVerifyLaunch verify_batch_launch(const slime_rs_batch* batch, const uint32_t* src, const uint32_t* cmp,
+                                              uint64_t* mismatches, uint64_t* first) {
+  RaggedVerifyLaunch v{};
+  v.in = src;
+  v.cmp = cmp;
+  v.desc = batch->d_desc;
+  v.units = batch->d_units;
+  v.tails = batch->d_tails;
+  v.nunits = (uint32_t)batch->counts.units;
+  v.ntails = batch->counts.tails;
+  v.U = batch->g.U;
+  v.C = batch->g.C;
+  v.mismatches = mismatches;
+  v.first = first;
+  v.nobj = batch->counts.nobj;
+  v.k = batch->k;
+  v.vec_ok = aligned4(src) && aligned4(cmp);  // as slime_rs_plan_verify
+  return v;
+}
+
+int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, const uint32_t* cmp,
+                               uint64_t* mismatches, uint64_t* first, void* stream) {
+  if (!plan) return fail(Status::InvalidArg, "plan_verify_batch: null plan");
+  if (!batch) return fail(Status::InvalidArg, "plan_verify_batch: null batch");
+  if (plan->k != batch->k || plan->device != batch->device)
+    return fail(Status::InvalidArg, "plan_verify_batch: the batch was created for k = " + std::to_string(batch->k) +
+                                        " on device " + std::to_string(batch->device) + ", the plan has k = " +
+                                        std::to_string(plan->k) + " on device " + std::to_string(plan->device));
+  if (!mismatches || !first) return fail(Status::InvalidArg, "plan_verify_batch: null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, "plan_verify_batch: null buffer");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  RaggedVerifyLaunch v = verify_batch_launch(batch, src, cmp, mismatches, first);
+  v.coeff = plan->d_coeff;
+  v.in_idx = plan->d_in_idx;
+  v.out_idx = plan->d_out_idx;
+  v.rows = plan->rows;
+  // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
+  plan->executed.store(true, std::memory_order_relaxed);
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_verify_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src,
+                                  const uint32_t* cmp, uint64_t* mismatches, uint64_t* first, void* stream) {
+  if (!set) return fail(Status::InvalidArg, "planset_verify_batch: null set");
+  if (!batch) return fail(Status::InvalidArg, "planset_verify_batch: null batch");
+  if (!batch->planned)
+    return fail(Status::InvalidArg, "planset_verify_batch: the batch carries no plan indices "
+                                    "(create it with slime_rs_batch_create_planned)");
+  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
+    return fail(Status::InvalidArg, "planset_verify_batch: the batch was created for " + std::to_string(batch->nplans) +
+                                        " plans of k = " + std::to_string(batch->k) + " on device " +
+                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
+                                        " plans of k = " + std::to_string(set->k) + " on device " +
+                                        std::to_string(set->device));
+  if (!mismatches || !first) return fail(Status::InvalidArg, "planset_verify_batch: null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, "planset_verify_batch: null buffer");
+  if (batch->counts.nobj == 0) return 0;
+  RaggedVerifyLaunch v = verify_batch_launch(batch, src, cmp, mismatches, first);
+  v.table = set->d_table;
+  v.rows = set->max_rows;  // the result arrays' row stride
+  DeviceScope ds(set->device);
+  HIP_TRY(launch_verify_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
   if (!plan || !out_shards) return fail(Status::InvalidArg, "plan_set_outputs: bad args");
   // The table rewrite below is a synchronous copy that nothing orders against

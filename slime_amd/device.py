@@ -277,6 +277,34 @@ class Plan:
                                                 ctypes.c_void_p(dst.data_ptr() + 4 * dst_offset),
                                                 _stream_handle(self.device, stream)))
 
+    def verify_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: "Batch",
+                     stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+                     cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """Plan.verify over a ragged batch in one launch (slime_rs_plan_verify_batch): inputs are
+        read through each span's src side, stored rows through its dst side at the plan's output
+        shards; cmp may be src.  Returns (mismatches, first): int64 tensors of shape
+        (batch.nobj, rows), first a column inside the object or -1.  Objects with L == 0 and
+        N.NO_PLAN objects of a planned batch keep (0, -1).  Asynchronous; nothing but the two
+        results is written."""
+        for t in (src, cmp):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan's device")
+        if batch.device != self.device or batch.k != self.k:
+            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
+                             f"the plan has k={self.k} on device {self.device}")
+        batch._check_extent(src, src_offset, 0, self.in_max)
+        batch._check_extent(cmp, cmp_offset, 1, self.rows - 1 if self.out_max is None else self.out_max)
+        mism, first = _verify_results(batch.nobj, self.rows, self.device)
+        if batch.nobj == 0:
+            return mism, first  # no results: nothing to initialise, nothing to launch
+        N.check(lib.slime_rs_plan_verify_batch(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                                               ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+                                               ctypes.c_void_p(mism.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                                               _stream_handle(self.device, stream)))
+        return mism, first
+
     @staticmethod
     def _check_extent(t: torch.Tensor, off: int, lay: N.Layout, L: int, nobj: int, max_shard: int) -> None:
         # Host-side bounds check before launching a hand-written kernel.
@@ -453,6 +481,38 @@ class PlanSet:
         N.check(lib.slime_rs_planset_execute_batch(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
                                                    ctypes.c_void_p(dst.data_ptr() + 4 * dst_offset),
                                                    _stream_handle(self.device, stream)))
+
+    def verify_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: Batch,
+                     stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+                     cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """Plan.verify_batch with every object checked against its own plan of the set
+        (slime_rs_planset_verify_batch): after a repair sweep, or a scrub of degraded objects from
+        a different survivor set each.  Returns (mismatches, first) of shape
+        (batch.nobj, max_rows); rows at or past an object's own plan's row count, and N.NO_PLAN
+        objects, keep (0, -1).  Asynchronous; nothing but the two results is written."""
+        for t in (src, cmp):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan set's device")
+        if getattr(batch, "plans", None) is None:
+            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
+        if batch.device != self.device or batch.k != self.k or batch.nplans != self.nplans:
+            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
+                             f"the set has {self.nplans} plans of k={self.k} on device {self.device}")
+        # The set-wide highest shard indices: every object is checked as if it ran the widest plan.
+        batch._check_extent(src, src_offset, 0, self.in_max)
+        batch._check_extent(cmp, cmp_offset, 1, self.out_max)
+        mism, first = _verify_results(batch.nobj, self.max_rows, self.device)
+        if batch.nobj == 0:
+            return mism, first
+        N.check(lib.slime_rs_planset_verify_batch(self._h, batch._h,
+                                                  ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                                                  ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+                                                  ctypes.c_void_p(mism.data_ptr()),
+                                                  ctypes.c_void_p(first.data_ptr()),
+                                                  _stream_handle(self.device, stream)))
+        return mism, first
 
     def close(self) -> None:
         if self._h:
