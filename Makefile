@@ -22,14 +22,19 @@ REDOTEST := tests/cpp/redo_list_test
 RAGGEDTEST := tests/cpp/ragged_plan_test
 PLANSETTEST := tests/cpp/planset_table_test
 STEPTEST := tests/cpp/verify_step_test
+PROBETEST := tests/cpp/probe_layout_test
 PROXYLOAD := tools/libproxy_load.so
 
-all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROXYLOAD)
+all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(PROXYLOAD)
 
 # Proxy-level load generator over the C-ABI (bench.py host_path.pooled): C++ threads, no GIL.
 $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(LIB)
 	g++ -std=c++17 -O2 -g -Wall -Wextra -pthread -fPIC -shared -Iinclude -o $@ $< -Lslime_amd/lib -lslime_rs -ldl \
 	  -Wl,-rpath,'$$ORIGIN/../slime_amd/lib'
+
+# The placement probe's table and object layout (probe_layout.hpp), CPU only.
+$(PROBETEST): tests/cpp/probe_layout_test.cpp $(SRC)/probe_layout.hpp
+	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/probe_layout_test.cpp
 
 # The ragged batch's host work tables (ragged_plan.hpp), CPU only.
 $(RAGGEDTEST): tests/cpp/ragged_plan_test.cpp $(SRC)/ragged_plan.hpp
@@ -93,7 +98,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST)
+	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

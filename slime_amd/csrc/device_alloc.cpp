@@ -19,6 +19,7 @@
 #include "capi_common.hpp"
 #include "gfp_host.hpp"
 #include "kernels.hpp"
+#include "probe_layout.hpp"
 
 namespace slime {
 namespace {
@@ -115,20 +116,21 @@ int map_buffer(int device, uint64_t bytes, uint64_t chunk, void** va_out, DevBuf
 // and shows up in exactly this many-stream read/write mix (DESIGN.md
 // "Placement modes"); the buffer's contents are garbage either way.
 double placement_probe(int device, uint8_t* va, uint64_t bytes) {
-  constexpr uint32_t kNeed = 8, kTotal = 12, kRows = kTotal - kNeed, kObj = 128;
+  using namespace probe;  // kNeed, kTotal, kRows, kObj, kTableWords
   // The coefficient / index table goes in the buffer's last 4 KiB, past the
   // objects: no allocation (a hipMalloc / hipFree pair synchronises the
-  // device, and is not allowed while another thread captures a graph).
-  constexpr uint64_t kTableRoom = 4096;
-  if (bytes < 2 * kTableRoom) return 0;
-  const uint64_t L = ((bytes - kTableRoom) / 4 / kTotal / kObj) & ~(uint64_t)63;
-  if (L < 65536) return 0;
-  std::vector<uint32_t> table(kRows * 16 + 16, 0);
+  // device, and is not allowed while another thread captures a graph).  Its
+  // offset is 256-byte aligned whatever `bytes` is (probe_layout.hpp): the
+  // kernels read it with scalar loads, which drop an address's low bits.
+  const probe::Layout lay = probe::layout(bytes);
+  const uint64_t L = lay.L;
+  if (L == 0) return 0;
+  std::vector<uint32_t> table(kTableWords, 0);
   for (uint32_t i = 0; i < kRows; ++i)
     for (uint32_t j = 0; j < kNeed; ++j) table[i * 16 + j] = 0x9E3779B9u * (i * kNeed + j + 1) % kP;
   for (uint32_t j = 0; j < kNeed; ++j) table[kRows * 16 + j] = j;
   for (uint32_t i = 0; i < kRows; ++i) table[kRows * 16 + 8 + i] = kNeed + i;
-  uint32_t* const d = (uint32_t*)(va + bytes - kTableRoom);
+  uint32_t* const d = (uint32_t*)(va + lay.table_off);
   hipStream_t s = nullptr;
   hipEvent_t ev[3] = {};
   double best = 0;

@@ -155,3 +155,21 @@ def test_redo_list_counter_protocol_emulated():
     assert r.returncode == 0, r.stdout + r.stderr
     for name in ("TestRedoListFixedOrders", "TestRedoListConcurrent", "TestRedoListFits"):
         assert f"ok   {name}" in r.stdout
+
+
+PROBE_BIN = os.path.join(ROOT, "tests", "cpp", "probe_layout_test")
+
+
+def test_probe_layout_keeps_the_table_aligned_and_inside():
+    """slime_amd/csrc/probe_layout.hpp (where placement_probe puts its table):
+    for every bytes % 256 residue, around 402 MB, 512 MiB and 16 GiB +- 3, the
+    table's offset is a multiple of 256, the table ends inside the range, the
+    objects end at or before it and L is a multiple of 64; too-small ranges are
+    refused (L == 0).  The kernels read the table with scalar loads, which
+    ignore the low address bits: a table at `bytes - 4096` of an odd-sized
+    range shifted the shard indices and sent the walk outside the buffer."""
+    subprocess.run(["make", "-C", ROOT, "tests/cpp/probe_layout_test"], check=True, capture_output=True)
+    r = subprocess.run([PROBE_BIN], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    for name in ("TestEveryResidue", "TestAroundTheSizesCallersUse", "TestRefusals"):
+        assert f"ok   {name}" in r.stdout

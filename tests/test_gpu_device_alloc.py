@@ -192,6 +192,31 @@ def test_probe_placement_of_caller_buffers(torch_dev, caplog):
     torch.cuda.empty_cache()
 
 
+def test_probe_placement_of_an_odd_sized_range_stays_inside_it(torch_dev):
+    """A range of 512 MiB + 1 bytes: the probe's table offset is 256-byte
+    aligned for any byte count (probe_layout.hpp; it was `bytes - 4096`, which
+    the kernels' scalar loads rounded down, shifting the shard indices), so
+    the walk measures a rate and writes nothing behind the range -- neither
+    the byte right after it nor a 1 MiB guard."""
+    torch = torch_dev
+    from slime_amd import device as D
+    nbytes, guard = (512 << 20) + 1, 1 << 20
+    big = torch.empty(nbytes + guard, dtype=torch.uint8, device="cuda")
+    big[nbytes:] = 0xA5
+    torch.cuda.synchronize()
+    gbs = ctypes.c_double()
+    N.check(N.lib.slime_rs_probe_placement(ctypes.c_void_p(big.data_ptr()), nbytes, 0, ctypes.byref(gbs)))
+    torch.cuda.synchronize()
+    assert gbs.value > 0
+    assert bool((big[nbytes:] == 0xA5).all()), "the probe wrote behind its range"
+    del big
+    # the wrapper over a tensor whose whole storage is the odd-sized range
+    t = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    assert D.probe_placement(t) > 0
+    del t
+    torch.cuda.empty_cache()
+
+
 def test_plan_warns_once_about_an_unprobed_large_buffer(torch_dev, caplog):
     """A >= 16 GiB caller buffer handed to a plan without a placement probe is
     logged once (its placement decides the kernels' speed); device_empty
