@@ -296,8 +296,9 @@ int slime_rs_batch_destroy(slime_rs_batch_t batch);
  * 4-columns-per-lane kernel (dynamic schedule, or static where
  * slime_rs_plan_execute would take it); wider plans, and bases that are not
  * 4-byte aligned, run one column per lane (correct, not fast: there is no
- * matrix-core or k-template ragged kernel).  Also out of scope: ragged forms
- * of the byte-slot pipeline.  A batch made by
+ * matrix-core or k-template ragged kernel).  Stored chunk bytes take the
+ * byte launches below (slime_rs_decode_objects_batch); what remains out of
+ * scope there is a ragged byte encode and matrix-core forms.  A batch made by
  * slime_rs_batch_create_planned is accepted too: its plan indices are ignored
  * here, and its SLIME_RS_NO_PLAN objects are skipped. */
 int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
@@ -356,9 +357,9 @@ int slime_rs_batch_create_planned(int device, int k, const slime_rs_span_t *span
  * to its erased shards is the common call: each object is repaired in its own
  * slots.  Forms as slime_rs_plan_execute_batch: k <= 16 over 4-byte aligned
  * bases runs four columns a lane, anything else one column a lane.
- * Out of scope: plan sets for the byte-slot pipeline,
- * matrix-core or k-template planned kernels for wide codes, and sets mixing
- * different k. */
+ * The byte-slot twin is slime_rs_planset_decode_objects_batch.  Out of scope:
+ * a ragged byte encode, matrix-core forms (matrix-core or k-template planned
+ * kernels for wide codes, symbols or bytes), and sets mixing different k. */
 int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
                                    void *stream);
 
@@ -387,13 +388,74 @@ int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batc
  * not the batch's, and for the set form an unplanned batch or one whose nplans
  * differs from the set's.
  * Forms: k <= 16 over 4-byte aligned src and cmp runs four columns a lane,
- * anything else one column a lane (correct, not fast).  Out of scope:
- * matrix-core or k-template ragged verify for wide codes, ragged or planned
- * forms of slime_rs_verify_objects, locating which shard is wrong. */
+ * anything else one column a lane (correct, not fast).  The ragged and planned
+ * forms of slime_rs_verify_objects are slime_rs_verify_objects_batch and
+ * slime_rs_planset_verify_objects_batch below.  Out of scope: matrix-core
+ * forms (matrix-core or k-template ragged verify for wide codes), a ragged
+ * byte encode, locating which shard is wrong. */
 int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
                                const uint32_t *cmp, uint64_t *mismatches, uint64_t *first, void *stream);
 int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src,
                                   const uint32_t *cmp, uint64_t *mismatches, uint64_t *first, void *stream);
+
+/* ---- ragged byte objects: repair and scrub stored chunks in one launch --------
+ * The four ragged launches above over what a store holds: chunk BYTES, every
+ * 4-byte word big-endian and XOR-ed with its object's mapping value
+ * (MapFromGF; meta.File.MappingValue), as the byte-slot pipeline below reads
+ * and writes them.  A batch made by slime_rs_batch_create or
+ * slime_rs_batch_create_planned is used as it is: in these launches a span's
+ * offsets and strides count 4-byte words of chunk bytes, so chunk c of object
+ * o starts at src + 4*(src_off + c*src_shard_stride) bytes and holds 4*L_o
+ * bytes (dst and cmp likewise with dst_off, dst_shard_stride).  One batch
+ * serves the symbol launches and the byte launches alike.
+ * mapping: a device array of the batch's nobj words; mapping[o] may be any
+ * uint32 (0, 1<<31 or a random fallback value).  Entries of objects with
+ * L == 0 or SLIME_RS_NO_PLAN are not read for their value.
+ * Decode: for every object o with work, row i of its plan and b < L_o, with
+ * m = mapping[o]: out[o][out_idx[i]] word b = BE(((sum_j coeff[i][j] *
+ * (BE(in[o][in_idx[j]] word b) ^ m)) mod p) ^ m) -- bit-identical to
+ * slime_rs_decode_objects_chunked run on that object alone with its plan.
+ * Input words at or above p after the XOR (corrupt chunks) are accepted and
+ * reduced exactly as the uniform byte decode reduces them.  dst may be src
+ * with the outputs in each object's own chunk slots: dst == src and every
+ * plan's outputs set to its erased chunks is the common call.  The set form
+ * takes the plan named by each object's descriptor, as
+ * slime_rs_planset_execute_batch does.
+ * Verify: slime_rs_verify_objects's rule per span -- a column mismatches iff
+ * BE(stored word) != computed ^ m (a stored BE((computed + p) ^ m) counts).
+ * The result arrays follow slime_rs_plan_verify_batch and
+ * slime_rs_planset_verify_batch in every respect: nobj x rows (set: nobj x
+ * max_rows) uint64, first a column inside the object or UINT64_MAX, both
+ * initialised by the call whenever nobj > 0, entries of objects without work
+ * and of rows past an object's plan keep (0, UINT64_MAX), nothing else
+ * written, no scratch, more than 64 rows in row blocks of 64.
+ * Asynchronous, and capturable under exactly the rules of
+ * slime_rs_plan_execute_batch (static walk inside captures at
+ * slime_rs_kernel_schedule 1, dynamic with a graph-held counter set at 2).
+ * The single-plan forms mark the plan as launched and accept a planned batch;
+ * the set forms mark nothing.  An empty batch launches nothing (verify: only
+ * the initialisation).  SLIME_RS_ERR_INVALID_ARG: null arguments -- decode's
+ * buffers and every mapping only when the batch has work, verify's buffers
+ * and result arrays always, as the symbol twins --, a plan or set whose k or
+ * device is not the batch's, and for the set forms an unplanned batch or one
+ * whose nplans differs from the set's.
+ * Forms: k <= 16 over 4-byte aligned src and dst (cmp) runs four columns a
+ * lane on the walks of the symbol launches, with the byte swap and the XOR
+ * applied where a tile's registers are consumed; anything else one column a
+ * lane (correct, not fast).  Out of scope: a ragged byte encode (MapToGF's
+ * speculative pass and mid-object switch are a project of their own; ingest
+ * batches by size class), matrix-core forms or k-template ragged byte kernels
+ * for wide codes, the host entry points and digests. */
+int slime_rs_decode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t *src, uint8_t *dst,
+                                  const uint32_t *mapping, void *stream);
+int slime_rs_planset_decode_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
+                                          uint8_t *dst, const uint32_t *mapping, void *stream);
+int slime_rs_verify_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t *src,
+                                  const uint8_t *cmp, const uint32_t *mapping, uint64_t *mismatches, uint64_t *first,
+                                  void *stream);
+int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
+                                          const uint8_t *cmp, const uint32_t *mapping, uint64_t *mismatches,
+                                          uint64_t *first, void *stream);
 
 /* ==== fused byte-domain object pipeline (writeChunks / reconstruct on device) ====
  * Object slots: object o's slot starts at slots + o*slot_stride bytes and holds

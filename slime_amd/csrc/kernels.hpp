@@ -376,6 +376,59 @@ hipError_t launch_verify_ragged(const RaggedVerifyLaunch& v, hipStream_t stream)
 // rs_verify_init_kernel on the stream, a kernel node in a capture (rs_verify.hip).
 hipError_t launch_verify_init(uint64_t* mismatches, uint64_t* first, uint64_t n, hipStream_t stream);
 
+// --- ragged byte objects (rs_bytes_ragged.hip) ----------------------------------
+// launch_apply_ragged / launch_apply_planned over stored chunk bytes: a word
+// is big-endian and XOR-ed with mapping[o] (the byte kernels' framing), the
+// descriptors' offsets and strides count 4-byte words of chunk bytes from
+// in / out.  For every object o with work, its plan's rows i and b < L_o:
+//   out word = BE(((sum_j coeff[i][j] * (BE(in word) ^ m)) mod p) ^ m), m = mapping[o].
+//   table == nullptr: one plan (coeff / in_idx / out_idx, `rows` rows);
+//   table != nullptr: a plan set's table, object o decoded with plan desc[o].reserved[0].
+// Forms, schedules and capture rules are launch_apply_ragged's.
+struct RaggedBytesLaunch {
+  const uint8_t* in;
+  uint8_t* out;
+  const ragged::Desc* desc;
+  const ragged::Unit* units;
+  const ragged::Tail* tails;
+  uint32_t nunits;
+  uint64_t ntails;
+  int U, C;
+  const uint32_t* coeff = nullptr;
+  const uint32_t* in_idx = nullptr;
+  const uint32_t* out_idx = nullptr;
+  const uint32_t* table = nullptr;
+  const uint32_t* mapping;  // nobj mapping values (device)
+  uint32_t rows, k;
+  bool vec_ok;
+};
+hipError_t launch_decode_bytes_ragged(const RaggedBytesLaunch& a, hipStream_t stream);
+
+// launch_verify_ragged over stored chunk bytes: a column of row i mismatches
+// iff BE(stored word) != computed ^ mapping[o].  Result arrays, row blocks and
+// everything else as RaggedVerifyLaunch.
+struct RaggedBytesVerifyLaunch {
+  const uint8_t* in;
+  const uint8_t* cmp;
+  const ragged::Desc* desc;
+  const ragged::Unit* units;
+  const ragged::Tail* tails;
+  uint32_t nunits;
+  uint64_t ntails;
+  int U, C;
+  const uint32_t* coeff = nullptr;
+  const uint32_t* in_idx = nullptr;
+  const uint32_t* out_idx = nullptr;
+  const uint32_t* table = nullptr;
+  const uint32_t* mapping;  // nobj mapping values (device)
+  uint64_t* mismatches;
+  uint64_t* first;
+  uint64_t nobj;
+  uint32_t rows, k;
+  bool vec_ok;
+};
+hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStream_t stream);
+
 // --- small host<->device transfers as one kernel (host_blit.hip) ----------
 // dst/src: device addresses (device memory, or pinned host memory mapped
 // into the device's address space); any alignment.

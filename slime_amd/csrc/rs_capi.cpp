@@ -824,6 +824,145 @@ int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch
   return 0;
 }
 
+// ---- ragged byte objects (rs_bytes_ragged.hip) --------------------------------------
+// The four ragged launches over stored chunk bytes; validation as their symbol twins.
+
+// The checks both plan forms share; `what` names the entry point.
+static int check_batch_plan(const char* what, const slime_rs_plan* plan, const slime_rs_batch* batch) {
+  if (!plan) return fail(Status::InvalidArg, std::string(what) + ": null plan");
+  if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
+  if (plan->k != batch->k || plan->device != batch->device)
+    return fail(Status::InvalidArg, std::string(what) + ": the batch was created for k = " + std::to_string(batch->k) +
+                                        " on device " + std::to_string(batch->device) + ", the plan has k = " +
+                                        std::to_string(plan->k) + " on device " + std::to_string(plan->device));
+  return 0;
+}
+
+static int check_batch_set(const char* what, const slime_rs_planset* set, const slime_rs_batch* batch) {
+  if (!set) return fail(Status::InvalidArg, std::string(what) + ": null set");
+  if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
+  if (!batch->planned)
+    return fail(Status::InvalidArg, std::string(what) + ": the batch carries no plan indices "
+                                                        "(create it with slime_rs_batch_create_planned)");
+  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
+    return fail(Status::InvalidArg, std::string(what) + ": the batch was created for " + std::to_string(batch->nplans) +
+                                        " plans of k = " + std::to_string(batch->k) + " on device " +
+                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
+                                        " plans of k = " + std::to_string(set->k) + " on device " +
+                                        std::to_string(set->device));
+  return 0;
+}
+
+static RaggedBytesLaunch decode_batch_launch(const slime_rs_batch* batch, const uint8_t* src, uint8_t* dst,
+                                             const uint32_t* mapping) {
+  RaggedBytesLaunch a{};
+  a.in = src;
+  a.out = dst;
+  a.desc = batch->d_desc;
+  a.units = batch->d_units;
+  a.tails = batch->d_tails;
+  a.nunits = (uint32_t)batch->counts.units;
+  a.ntails = batch->counts.tails;
+  a.U = batch->g.U;
+  a.C = batch->g.C;
+  a.mapping = mapping;
+  a.k = batch->k;
+  a.vec_ok = aligned4(src) && aligned4(dst);
+  return a;
+}
+
+static RaggedBytesVerifyLaunch verify_objects_launch(const slime_rs_batch* batch, const uint8_t* src,
+                                                     const uint8_t* cmp, const uint32_t* mapping,
+                                                     uint64_t* mismatches, uint64_t* first) {
+  RaggedBytesVerifyLaunch v{};
+  v.in = src;
+  v.cmp = cmp;
+  v.desc = batch->d_desc;
+  v.units = batch->d_units;
+  v.tails = batch->d_tails;
+  v.nunits = (uint32_t)batch->counts.units;
+  v.ntails = batch->counts.tails;
+  v.U = batch->g.U;
+  v.C = batch->g.C;
+  v.mapping = mapping;
+  v.mismatches = mismatches;
+  v.first = first;
+  v.nobj = batch->counts.nobj;
+  v.k = batch->k;
+  v.vec_ok = aligned4(src) && aligned4(cmp);
+  return v;
+}
+
+int slime_rs_decode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src, uint8_t* dst,
+                                  const uint32_t* mapping, void* stream) {
+  if (int rc = check_batch_plan("decode_objects_batch", plan, batch)) return rc;
+  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (!src || !dst) return fail(Status::InvalidArg, "decode_objects_batch: null buffer");
+  if (!mapping) return fail(Status::InvalidArg, "decode_objects_batch: null mapping");
+  RaggedBytesLaunch a = decode_batch_launch(batch, src, dst, mapping);
+  a.coeff = plan->d_coeff;
+  a.in_idx = plan->d_in_idx;
+  a.out_idx = plan->d_out_idx;
+  a.rows = plan->rows;
+  plan->executed.store(true, std::memory_order_relaxed);
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
+  return 0;
+}
+
+int slime_rs_planset_decode_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
+                                          uint8_t* dst, const uint32_t* mapping, void* stream) {
+  if (int rc = check_batch_set("planset_decode_objects_batch", set, batch)) return rc;
+  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (!src || !dst) return fail(Status::InvalidArg, "planset_decode_objects_batch: null buffer");
+  if (!mapping) return fail(Status::InvalidArg, "planset_decode_objects_batch: null mapping");
+  RaggedBytesLaunch a = decode_batch_launch(batch, src, dst, mapping);
+  a.table = set->d_table;
+  DeviceScope ds(set->device);
+  HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
+  return 0;
+}
+
+int slime_rs_verify_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src,
+                                  const uint8_t* cmp, const uint32_t* mapping, uint64_t* mismatches, uint64_t* first,
+                                  void* stream) {
+  if (int rc = check_batch_plan("verify_objects_batch", plan, batch)) return rc;
+  if (!mismatches || !first) return fail(Status::InvalidArg, "verify_objects_batch: null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, "verify_objects_batch: null buffer");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  // An empty batch launches only the initialisation, which reads no mapping.
+  if (!mapping && (batch->counts.units != 0 || batch->counts.tails != 0))
+    return fail(Status::InvalidArg, "verify_objects_batch: null mapping");
+  RaggedBytesVerifyLaunch v = verify_objects_launch(batch, src, cmp, mapping, mismatches, first);
+  v.coeff = plan->d_coeff;
+  v.in_idx = plan->d_in_idx;
+  v.out_idx = plan->d_out_idx;
+  v.rows = plan->rows;
+  // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
+  plan->executed.store(true, std::memory_order_relaxed);
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_verify_bytes_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
+                                          const uint8_t* cmp, const uint32_t* mapping, uint64_t* mismatches,
+                                          uint64_t* first, void* stream) {
+  if (int rc = check_batch_set("planset_verify_objects_batch", set, batch)) return rc;
+  if (!mismatches || !first) return fail(Status::InvalidArg, "planset_verify_objects_batch: null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, "planset_verify_objects_batch: null buffer");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  // An empty batch launches only the initialisation, which reads no mapping.
+  if (!mapping && (batch->counts.units != 0 || batch->counts.tails != 0))
+    return fail(Status::InvalidArg, "planset_verify_objects_batch: null mapping");
+  RaggedBytesVerifyLaunch v = verify_objects_launch(batch, src, cmp, mapping, mismatches, first);
+  v.table = set->d_table;
+  v.rows = set->max_rows;  // the result arrays' row stride
+  DeviceScope ds(set->device);
+  HIP_TRY(launch_verify_bytes_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
   if (!plan || !out_shards) return fail(Status::InvalidArg, "plan_set_outputs: bad args");
   // The table rewrite below is a synchronous copy that nothing orders against

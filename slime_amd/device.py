@@ -385,8 +385,9 @@ class Batch:
             return cls(spans, k, device), off
         return cls(spans, k, device, plans=plans, nplans=nplans), off
 
-    def _check_extent(self, t: torch.Tensor, off: int, side: int, max_shard: int) -> None:
+    def _check_extent(self, t: torch.Tensor, off: int, side: int, max_shard: int, unit: int = 1) -> None:
         # Host-side bounds check of every span before launching a hand-written kernel.
+        # unit: tensor elements per span element (4 for the byte launches over uint8 tensors).
         key = (side, max_shard)
         if key not in self._extents:
             s = self.spans.astype(object)  # Python ints: no 64-bit wrap
@@ -395,8 +396,8 @@ class Batch:
             ends = [(s[i, 2 * side] + max_shard * s[i, 2 * side + 1] + s[i, 4], i) for i in live]
             self._extents[key] = max(ends) if ends else (0, -1)
         last, o = self._extents[key]
-        if o >= 0 and (off < 0 or off + last > t.numel()):
-            raise ValueError(f"span {o} addresses element {off + last} of a {t.numel()}-element tensor")
+        if o >= 0 and (off < 0 or unit * (off + last) > t.numel()):
+            raise ValueError(f"span {o} addresses element {unit * (off + last)} of a {t.numel()}-element tensor")
 
     def close(self) -> None:
         if self._h:
@@ -661,4 +662,77 @@ def verify_objects(plan: Plan, slots: torch.Tensor, slot_stride: int, L: int, no
     N.check(lib.slime_rs_verify_objects(plan._h, ctypes.c_void_p(slots.data_ptr()), slot_stride, chunk_stride, L,
                                         nobj, ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(mism.data_ptr()),
                                         ctypes.c_void_p(first.data_ptr()), _stream_handle(dev, stream)))
+    return mism, first
+
+
+# ---- ragged byte objects: stored chunks of objects of different lengths in one launch ----
+
+def _check_objects_batch(what: str, plan_or_set, a: torch.Tensor, b: torch.Tensor, batch: "Batch",
+                         mapping: torch.Tensor) -> bool:
+    """The host-side checks of the two byte launches, all ValueError and all before any C call.
+    Returns whether plan_or_set is a PlanSet."""
+    is_set = isinstance(plan_or_set, PlanSet)
+    if not is_set and not isinstance(plan_or_set, Plan):
+        raise ValueError(f"{what} takes a Plan or a PlanSet")
+    dev = plan_or_set.device
+    for t in (a, b):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"{what}: chunk buffers must be contiguous uint8 tensors")
+        if _dev_index(t) != dev:
+            raise ValueError(f"{what}: tensor is not on the plan's device")
+    if is_set:
+        if getattr(batch, "plans", None) is None:
+            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
+        if batch.device != dev or batch.k != plan_or_set.k or batch.nplans != plan_or_set.nplans:
+            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
+                             f"the set has {plan_or_set.nplans} plans of k={plan_or_set.k} on device {dev}")
+        out_max = plan_or_set.out_max  # set-wide: every object is checked as if it ran the widest plan
+    else:
+        if batch.device != dev or batch.k != plan_or_set.k:
+            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
+                             f"the plan has k={plan_or_set.k} on device {dev}")
+        out_max = plan_or_set.rows - 1 if plan_or_set.out_max is None else plan_or_set.out_max
+    # A span's offsets and strides count 4-byte words of chunk bytes.
+    batch._check_extent(a, 0, 0, plan_or_set.in_max, unit=4)
+    batch._check_extent(b, 0, 1, out_max, unit=4)
+    if (mapping.dtype not in (torch.int32, torch.uint32) or not mapping.is_contiguous()
+            or mapping.numel() < batch.nobj or _dev_index(mapping) != dev):
+        raise ValueError(f"{what}: mapping needs {batch.nobj} contiguous int32/uint32 words on the plan's device")
+    return is_set
+
+
+def decode_objects_batch(plan_or_set, src: torch.Tensor, dst: torch.Tensor, batch: Batch, mapping: torch.Tensor,
+                         stream: Optional[torch.cuda.Stream] = None) -> None:
+    """decode_objects over a ragged batch of stored chunks in one launch
+    (slime_rs_decode_objects_batch; with a PlanSet and a planned batch every object takes its own
+    plan, slime_rs_planset_decode_objects_batch).  src and dst are uint8 tensors of chunk bytes;
+    a span's offsets and strides count 4-byte words, so chunk c of object o starts at byte
+    4 * (off + c * shard_stride).  mapping[o] is object o's MappingValue.  dst may be src
+    (each object repaired in its own chunk slots).  Asynchronous."""
+    is_set = _check_objects_batch("decode_objects_batch", plan_or_set, src, dst, batch, mapping)
+    _note_unprobed(src)
+    if dst.data_ptr() != src.data_ptr():
+        _note_unprobed(dst)
+    call = lib.slime_rs_planset_decode_objects_batch if is_set else lib.slime_rs_decode_objects_batch
+    N.check(call(plan_or_set._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+                 ctypes.c_void_p(mapping.data_ptr()), _stream_handle(plan_or_set.device, stream)))
+
+
+def verify_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, mapping: torch.Tensor,
+                         stream: Optional[torch.cuda.Stream] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """verify_objects over a ragged batch of stored chunks in one launch
+    (slime_rs_verify_objects_batch / slime_rs_planset_verify_objects_batch): inputs are read
+    through each span's src side, stored chunks through its dst side; cmp may be src.  Returns
+    (mismatches, first) exactly as Plan.verify_batch / PlanSet.verify_batch do: shape
+    (batch.nobj, rows) or (batch.nobj, max_rows), first a column inside the object or -1.
+    Asynchronous; nothing but the two results is written."""
+    is_set = _check_objects_batch("verify_objects_batch", plan_or_set, src, cmp, batch, mapping)
+    rows = plan_or_set.max_rows if is_set else plan_or_set.rows
+    mism, first = _verify_results(batch.nobj, rows, plan_or_set.device)
+    if batch.nobj == 0:
+        return mism, first  # no results: nothing to initialise, nothing to launch
+    call = lib.slime_rs_planset_verify_objects_batch if is_set else lib.slime_rs_verify_objects_batch
+    N.check(call(plan_or_set._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(cmp.data_ptr()),
+                 ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(mism.data_ptr()),
+                 ctypes.c_void_p(first.data_ptr()), _stream_handle(plan_or_set.device, stream)))
     return mism, first
