@@ -297,8 +297,9 @@ int slime_rs_batch_destroy(slime_rs_batch_t batch);
  * slime_rs_plan_execute would take it); wider plans, and bases that are not
  * 4-byte aligned, run one column per lane (correct, not fast: there is no
  * matrix-core or k-template ragged kernel).  Stored chunk bytes take the
- * byte launches below (slime_rs_decode_objects_batch); what remains out of
- * scope there is a ragged byte encode and matrix-core forms.  A batch made by
+ * byte launches below (slime_rs_decode_objects_batch, and the ragged byte
+ * encode, slime_rs_encode_objects_batch); what remains out of scope there is
+ * matrix-core forms.  A batch made by
  * slime_rs_batch_create_planned is accepted too: its plan indices are ignored
  * here, and its SLIME_RS_NO_PLAN objects are skipped. */
 int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
@@ -357,9 +358,10 @@ int slime_rs_batch_create_planned(int device, int k, const slime_rs_span_t *span
  * to its erased shards is the common call: each object is repaired in its own
  * slots.  Forms as slime_rs_plan_execute_batch: k <= 16 over 4-byte aligned
  * bases runs four columns a lane, anything else one column a lane.
- * The byte-slot twin is slime_rs_planset_decode_objects_batch.  Out of scope:
- * a ragged byte encode, matrix-core forms (matrix-core or k-template planned
- * kernels for wide codes, symbols or bytes), and sets mixing different k. */
+ * The byte-slot twin is slime_rs_planset_decode_objects_batch; the ragged byte
+ * encode (slime_rs_encode_objects_batch) takes one plan, not a set.  Out of
+ * scope: matrix-core forms (matrix-core or k-template planned kernels for wide
+ * codes, symbols or bytes), and sets mixing different k. */
 int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src, uint32_t *dst,
                                    void *stream);
 
@@ -390,9 +392,10 @@ int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batc
  * Forms: k <= 16 over 4-byte aligned src and cmp runs four columns a lane,
  * anything else one column a lane (correct, not fast).  The ragged and planned
  * forms of slime_rs_verify_objects are slime_rs_verify_objects_batch and
- * slime_rs_planset_verify_objects_batch below.  Out of scope: matrix-core
- * forms (matrix-core or k-template ragged verify for wide codes), a ragged
- * byte encode, locating which shard is wrong. */
+ * slime_rs_planset_verify_objects_batch below, and what they scrub is written
+ * by the ragged byte encode (slime_rs_encode_objects_batch).  Out of scope:
+ * matrix-core forms (matrix-core or k-template ragged verify for wide codes),
+ * locating which shard is wrong. */
 int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
                                const uint32_t *cmp, uint64_t *mismatches, uint64_t *first, void *stream);
 int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src,
@@ -442,10 +445,10 @@ int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch
  * Forms: k <= 16 over 4-byte aligned src and dst (cmp) runs four columns a
  * lane on the walks of the symbol launches, with the byte swap and the XOR
  * applied where a tile's registers are consumed; anything else one column a
- * lane (correct, not fast).  Out of scope: a ragged byte encode (MapToGF's
- * speculative pass and mid-object switch are a project of their own; ingest
- * batches by size class), matrix-core forms or k-template ragged byte kernels
- * for wide codes, the host entry points and digests. */
+ * lane (correct, not fast).  Writing such chunks is the ragged byte encode
+ * below (slime_rs_encode_objects_batch).  Out of scope: matrix-core forms or
+ * k-template ragged byte kernels for wide codes, the host entry points and
+ * digests. */
 int slime_rs_decode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t *src, uint8_t *dst,
                                   const uint32_t *mapping, void *stream);
 int slime_rs_planset_decode_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
@@ -456,6 +459,70 @@ int slime_rs_verify_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, 
 int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
                                           const uint8_t *cmp, const uint32_t *mapping, uint64_t *mismatches,
                                           uint64_t *first, void *stream);
+
+/* ---- ragged byte encode: ingest objects of different sizes in one launch -------
+ * slime_rs_encode_objects over the spans of a batch, each object with its own
+ * size: the write side of the four launches above.  The batch
+ * (slime_rs_batch_create or _create_planned) is used as it is, under the byte
+ * launches' layout rule: data chunk j of object o is the 4*L_o bytes at
+ * src + 4*(src_off + j*src_shard_stride), parity row i goes to
+ * dst + 4*(dst_off + out_idx[i]*dst_shard_stride).  dst may be src: in-place
+ * slots with the plan's outputs set to need..total-1 is the common call.  The
+ * plan must read inputs 0..k-1 in that order (slime_rs_plan_encode gives such a
+ * plan), because padding depends on a chunk's position in the object; anything
+ * else is SLIME_RS_ERR_INVALID_ARG.  A planned batch is accepted: its plan
+ * indices are ignored and its SLIME_RS_NO_PLAN objects are skipped.
+ * sizes: a device array of nobj uint64, object o's byte length S with
+ * slime_rs_chunk_size(S, k) == 4*L_o.  The kernels clamp the object's word
+ * count to k*L_o, so a wrong size never makes a launch touch a byte outside
+ * the object's own chunks; what such an object encodes to is unspecified.
+ * Entries of objects without work are not read.
+ * Arithmetic, per object, exactly slime_rs_encode_objects's (map.go:15-67,
+ * multi_store.go:271-296, :526-554): word w < nw = ceil(S/4) is BE(bytes), a
+ * partial last word masked to its valid high bytes; words nw..kL-1 are symbol
+ * 0 and are not XOR-ed; parity word = BE(row ^ m); the data-chunk tail is
+ * REWRITTEN IN src: BE(packed) for the partial word, BE(m) for every padding
+ * word.  Bytes past S inside the object's data chunks may be garbage on entry:
+ * they neither raise a flag nor survive.
+ * mapping, status: device arrays of nobj words, both initialised by the call
+ * for every object, on the stream.  mapping[o] receives MapToGF's choice;
+ * status[o] = 1 marks an object that needs the random fallback (its parity is
+ * not final until slime_rs_resolve_fallbacks_batch).  After either call
+ * returns its work to the stream a caller sees only 0 or 1 in status.
+ * slime_rs_encode_objects_batch is asynchronous, reads and writes device
+ * memory only and takes no scratch.  It is several kernel nodes in a linear
+ * chain (initialisation, the speculative pass with m = 0, the choice of
+ * mapping, the re-encode of the objects whose mapping is not 0, a clean-up),
+ * capturable under exactly the rules of slime_rs_plan_execute_batch (static
+ * walk at slime_rs_kernel_schedule 1, dynamic with graph-held counter sets at
+ * 2; each dynamic pass takes its own set).  It marks the plan launched.  An
+ * empty batch launches only the initialisation.  SLIME_RS_ERR_INVALID_ARG:
+ * null handles, a plan whose k or device is not the batch's, null mapping or
+ * status, and -- when the batch has work -- null buffers or sizes.
+ * slime_rs_encode_objects_batch_phased records phase_event (a hipEvent_t, or
+ * NULL) on the stream after the speculative pass, for measurements.
+ * slime_rs_resolve_fallbacks_batch is synchronous, like
+ * slime_rs_resolve_fallbacks: it reads status, finds a mapping for every object
+ * with status 1 (64 candidates a device pass from the stream slime_gf_seed
+ * steers; the first non-zero fit wins), writes mapping[o], re-encodes only
+ * those objects -- one launch for all of them -- and clears their status;
+ * *resolved (optional) = objects fixed.  SLIME_RS_ERR_MAPPING_FALLBACK as the
+ * uniform call; nothing has been written then.
+ * Forms: k <= 16 over 4-byte aligned src and dst runs four columns a lane on
+ * the walks of slime_rs_decode_objects_batch over each object's interior (no
+ * partial word or padding), and one column a lane over its at most k + 3 edge
+ * columns; anything else one column a lane (correct, not fast).  Out of scope:
+ * the mid-object switch, redo lists and top-bit correction for ragged objects
+ * (a switched object is re-encoded whole), a matrix-core or k-template ragged
+ * encode, a plan-set encode, host entry points and digests. */
+int slime_rs_encode_objects_batch(slime_rs_plan_t encode_plan, slime_rs_batch_t batch, uint8_t *src, uint8_t *dst,
+                                  const uint64_t *sizes, uint32_t *mapping, uint32_t *status, void *stream);
+int slime_rs_encode_objects_batch_phased(slime_rs_plan_t encode_plan, slime_rs_batch_t batch, uint8_t *src,
+                                         uint8_t *dst, const uint64_t *sizes, uint32_t *mapping, uint32_t *status,
+                                         void *stream, void *phase_event);
+int slime_rs_resolve_fallbacks_batch(slime_rs_plan_t encode_plan, slime_rs_batch_t batch, uint8_t *src, uint8_t *dst,
+                                     const uint64_t *sizes, uint32_t *mapping, uint32_t *status, void *stream,
+                                     int *resolved);
 
 /* ==== fused byte-domain object pipeline (writeChunks / reconstruct on device) ====
  * Object slots: object o's slot starts at slots + o*slot_stride bytes and holds

@@ -429,6 +429,42 @@ struct RaggedBytesVerifyLaunch {
 };
 hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStream_t stream);
 
+// --- ragged byte encode (rs_bytes_ragged_encode.hip) ------------------------------
+// The fused byte encode over a ragged batch: object o of sizes[o] bytes, its k
+// data chunks read (and their tails rewritten) through the descriptor's src
+// side, the plan's rows written through its dst side.  The plan reads inputs
+// 0 .. k-1 in that order (the host checks it), so no in_idx.  A call is the
+// steps below in order on one stream; slime_rs_resolve_fallbacks_batch marks
+// objects kRaggedEncodePending itself and runs Pass1 and Clear.  Forms,
+// schedules and capture rules are launch_decode_bytes_ragged's; each dynamic
+// pass takes its own counter set.
+constexpr uint32_t kRaggedEncodePending = 2u;  // status: re-encode with mapping[o] (transient)
+enum class RaggedEncodeStep {
+  Init,    // mapping[o] = status[o] = 0
+  Pass0,   // m = 0 for every object with work; MapToGF's flag bits OR-ed into status[o]
+  Select,  // flags -> mapping[o]; status[o] = 1 (fallback), 0, or kRaggedEncodePending
+  Pass1,   // the pending objects again with m = mapping[o]
+  Clear    // kRaggedEncodePending -> 0
+};
+struct RaggedEncodeLaunch {
+  uint8_t* src;
+  uint8_t* dst;
+  const ragged::Desc* desc;
+  const ragged::Unit* units;
+  uint32_t nunits;
+  uint32_t nobj;
+  bool has_work;  // some object has columns (units or tails)
+  int U, C;
+  const uint32_t* coeff;
+  const uint32_t* out_idx;
+  const uint64_t* sizes;  // nobj object sizes in bytes (device)
+  uint32_t* mapping;      // nobj words (device)
+  uint32_t* status;       // nobj words (device)
+  uint32_t rows, k;
+  bool vec_ok;
+};
+hipError_t launch_encode_bytes_ragged(const RaggedEncodeLaunch& a, RaggedEncodeStep step, hipStream_t stream);
+
 // --- small host<->device transfers as one kernel (host_blit.hip) ----------
 // dst/src: device addresses (device memory, or pinned host memory mapped
 // into the device's address space); any alignment.

@@ -1255,6 +1255,140 @@ extern "C" int slime_rs_resolve_fallbacks(slime_rs_plan_t plan, uint8_t* slots, 
                                             resolved);
 }
 
+// ---- ragged byte encode (rs_bytes_ragged_encode.hip) ---------------------------------
+
+// The checks and the launch record both calls share; `what` names the entry point.
+static int encode_batch_launch(const char* what, slime_rs_plan* plan, const slime_rs_batch* batch, uint8_t* src,
+                               uint8_t* dst, const uint64_t* sizes, uint32_t* mapping, uint32_t* status,
+                               RaggedEncodeLaunch* a) {
+  if (int rc = check_batch_plan(what, plan, batch)) return rc;
+  if (!plan->in_seq)
+    return fail(Status::InvalidArg, std::string(what) + ": the plan must read inputs 0..k-1 in that order "
+                                                        "(slime_rs_plan_encode): padding depends on a chunk's position");
+  if (!mapping || !status) return fail(Status::InvalidArg, std::string(what) + ": null mapping/status");
+  const bool work = batch->counts.units != 0 || batch->counts.tails != 0;
+  if (work && (!src || !dst)) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  if (work && !sizes) return fail(Status::InvalidArg, std::string(what) + ": null sizes");
+  *a = RaggedEncodeLaunch{};
+  a->src = src;
+  a->dst = dst;
+  a->desc = batch->d_desc;
+  a->units = batch->d_units;
+  a->nunits = (uint32_t)batch->counts.units;
+  a->nobj = (uint32_t)batch->counts.nobj;
+  a->has_work = work;
+  a->U = batch->g.U;
+  a->C = batch->g.C;
+  a->coeff = plan->d_coeff;
+  a->out_idx = plan->d_out_idx;
+  a->sizes = sizes;
+  a->mapping = mapping;
+  a->status = status;
+  a->rows = plan->rows;
+  a->k = plan->k;
+  a->vec_ok = aligned4(src) && aligned4(dst);
+  return 0;
+}
+
+int slime_rs_encode_objects_batch_phased(slime_rs_plan_t plan, slime_rs_batch_t batch, uint8_t* src, uint8_t* dst,
+                                         const uint64_t* sizes, uint32_t* mapping, uint32_t* status, void* stream,
+                                         void* phase_event) {
+  RaggedEncodeLaunch a;
+  if (int rc = encode_batch_launch("encode_objects_batch", plan, batch, src, dst, sizes, mapping, status, &a)) return rc;
+  if (a.nobj == 0) return 0;  // nothing to initialise, nothing to launch
+  hipStream_t s = (hipStream_t)stream;
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Init, s));
+  if (!a.has_work) return 0;  // an empty batch: nothing but the initialisation, which reads no plan table
+  plan->executed.store(true, std::memory_order_relaxed);
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Pass0, s));
+  if (phase_event) HIP_TRY(hipEventRecord((hipEvent_t)phase_event, s));
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Select, s));
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Pass1, s));
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Clear, s));
+  return 0;
+}
+
+int slime_rs_encode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, uint8_t* src, uint8_t* dst,
+                                  const uint64_t* sizes, uint32_t* mapping, uint32_t* status, void* stream) {
+  return slime_rs_encode_objects_batch_phased(plan, batch, src, dst, sizes, mapping, status, stream, nullptr);
+}
+
+int slime_rs_resolve_fallbacks_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, uint8_t* src, uint8_t* dst,
+                                     const uint64_t* sizes, uint32_t* mapping, uint32_t* status, void* stream,
+                                     int* resolved) {
+  if (resolved) *resolved = 0;
+  RaggedEncodeLaunch a;
+  if (int rc = encode_batch_launch("resolve_fallbacks_batch", plan, batch, src, dst, sizes, mapping, status, &a))
+    return rc;
+  if (a.nobj == 0 || !a.has_work) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceScope ds(plan->device);
+  const uint64_t nobj = a.nobj;
+  std::vector<uint32_t> st(nobj);
+  HIP_TRY(hipMemcpyAsync(st.data(), status, nobj * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  constexpr uint32_t kCand = kMapCandidates;
+  WsLease lease;
+  std::vector<std::pair<uint64_t, uint32_t>> fixed;  // {object, mapping}
+  for (uint64_t o = 0; o < nobj; ++o) {
+    if (st[o] != 1) continue;
+    // The object's span and size, from the device tables (fallback objects are rare).
+    ragged::Desc d;
+    uint64_t S = 0;
+    HIP_TRY(hipMemcpyAsync(&d, batch->d_desc + o, sizeof(d), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&S, sizes + o, sizeof(S), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t L = d.ncols;
+    if (L == 0) continue;  // no work: nothing set this status
+    const uint64_t cap = (uint64_t)plan->k * L * 4;
+    if (S > cap) S = cap;  // the kernels' clamp
+    const uint64_t nw = (S + 3) / 4;
+    if (!lease.ws)
+      if (int rc = acquire_ws(plan->device, &lease.ws)) return rc;
+    if (int rc = lease.ws->reserve(round16(nw * 4) + 2 * kCand * 4)) return rc;
+    uint32_t* d_words = (uint32_t*)lease.ws->dbuf;
+    uint32_t* d_cand = (uint32_t*)(lease.ws->dbuf + round16(nw * 4));
+    uint32_t* d_bad = d_cand + kCand;
+    // the object's words, data chunk by data chunk at the span's addresses (object byte i is in chunk i / 4L)
+    for (uint64_t j = 0; j * 4 * L < S; ++j)
+      HIP_TRY(launch_map_pack(src + ((d.src_off + j * d.src_shard) << 2), std::min<uint64_t>(4 * L, S - j * 4 * L), 0,
+                              d_words + j * L, nullptr, s));
+    uint32_t m = 0;
+    bool found = false;
+    for (int round = 0; round < (1 << 16) && !found; ++round) {
+      uint32_t cand[kCand], bad[kCand];
+      draw_candidates(cand, kCand);
+      HIP_TRY(hipMemcpyAsync(d_cand, cand, sizeof(cand), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(bad), s));
+      HIP_TRY(launch_mapping_probe(d_words, nw, d_cand, kCand, d_bad, s));
+      HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (uint32_t c = 0; c < kCand && !found; ++c)
+        if (!bad[c] && cand[c] != 0) {
+          m = cand[c];
+          found = true;
+        }
+    }
+    // Nothing was written yet: every status is still 0 or 1.
+    if (!found) return status_of(Status::MappingFallback, "resolve_fallbacks_batch");
+    fixed.emplace_back(o, m);
+  }
+  if (fixed.empty()) return 0;
+  // Mark the resolved objects pending, re-encode exactly those in one launch, clear the mark.
+  const uint32_t pending = kRaggedEncodePending;
+  for (const auto& f : fixed) {
+    HIP_TRY(hipMemcpyAsync(mapping + f.first, &f.second, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(status + f.first, &pending, 4, hipMemcpyHostToDevice, s));
+  }
+  plan->executed.store(true, std::memory_order_relaxed);
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Pass1, s));
+  HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Clear, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the mapping values and `pending` live on this frame
+  if (resolved) *resolved = (int)fixed.size();
+  return 0;
+}
+
 extern "C" int slime_rs_decode_objects_chunked(slime_rs_plan_t plan, uint8_t* slots, uint64_t slot_stride,
                                                uint64_t chunk_stride, uint64_t L, uint64_t nobj,
                                                const uint32_t* mapping, void* stream) {

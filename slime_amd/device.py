@@ -736,3 +736,94 @@ def verify_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batc
                  ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(mism.data_ptr()),
                  ctypes.c_void_p(first.data_ptr()), _stream_handle(plan_or_set.device, stream)))
     return mism, first
+
+
+# ---- ragged byte encode: objects of different sizes ingested in one launch ----
+
+def _encode_batch_args(what: str, plan, src: torch.Tensor, dst: torch.Tensor, batch: "Batch", sizes,
+                       mapping: Optional[torch.Tensor], status: Optional[torch.Tensor],
+                       stream: Optional[torch.cuda.Stream] = None):
+    """The host-side checks of the ragged byte encode calls, all ValueError and all before any C
+    call: _check_objects_batch's, the same for status, and sizes -- a device tensor of batch.nobj
+    int64/uint64 entries, or a host sequence, which is checked against every working span's L
+    (slime_rs_chunk_size(S, k) == 4 L) and uploaded on the launch's stream.  Returns (sizes,
+    mapping, status) tensors."""
+    if not isinstance(plan, Plan):
+        raise ValueError(f"{what} takes a Plan (slime_rs_plan_encode), not a PlanSet")
+    if mapping is None:  # the call initialises both on its stream
+        mapping = torch.empty(batch.nobj, dtype=torch.int32, device=src.device)
+    if status is None:
+        status = torch.empty(batch.nobj, dtype=torch.int32, device=src.device)
+    _check_objects_batch(what, plan, src, dst, batch, mapping)
+    if (status.dtype not in (torch.int32, torch.uint32) or not status.is_contiguous()
+            or status.numel() < batch.nobj or _dev_index(status) != plan.device):
+        raise ValueError(f"{what}: status needs {batch.nobj} contiguous int32/uint32 words on the plan's device")
+    if isinstance(sizes, torch.Tensor):
+        if (sizes.dtype not in (torch.int64, torch.uint64) or not sizes.is_contiguous()
+                or sizes.numel() < batch.nobj or _dev_index(sizes) != plan.device):
+            raise ValueError(f"{what}: sizes needs {batch.nobj} contiguous int64/uint64 entries on the plan's device")
+    else:
+        host = [int(s) for s in sizes]
+        if len(host) < batch.nobj:
+            raise ValueError(f"{what}: sizes needs {batch.nobj} entries, got {len(host)}")
+        plans = getattr(batch, "plans", None)
+        for o in range(batch.nobj):
+            L = int(batch.spans[o, 4])
+            if L == 0 or (plans is not None and plans[o] == N.NO_PLAN):
+                host[o] = 0  # no work: the entry is not read
+                continue
+            if host[o] < 0 or -(-(-(-host[o] // 4)) // batch.k) != L:
+                raise ValueError(f"{what}: object {o} of {host[o]} bytes has chunks of "
+                                 f"{-(-(-(-host[o] // 4)) // batch.k)} words at k={batch.k}, its span has L={L}")
+        if stream is None:
+            sizes = torch.tensor(host[:batch.nobj], dtype=torch.int64).to(src.device)
+        else:
+            with torch.cuda.stream(stream):  # the upload ahead of the launch on its own stream
+                sizes = torch.tensor(host[:batch.nobj], dtype=torch.int64).to(src.device)
+    return sizes, mapping, status
+
+
+def encode_objects_batch(plan: Plan, src: torch.Tensor, dst: torch.Tensor, batch: Batch, sizes,
+                         mapping: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                         stream: Optional[torch.cuda.Stream] = None,
+                         phase_event: Optional[torch.cuda.Event] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """encode_objects over a ragged batch in one launch (slime_rs_encode_objects_batch): object o
+    of sizes[o] bytes has its data chunks at the span's src side (byte 4 * (src_off + j *
+    src_shard_stride)) and gets its parity rows at the dst side; dst may be src.  plan reads
+    inputs 0..k-1 (Plan.encode).  The data-chunk tails are rewritten in src.  Returns (mapping,
+    status): MapToGF's choice per object, and 1 where resolve_fallbacks_batch has to finish the
+    object.  Asynchronous.  phase_event (a recorded torch.cuda.Event) is recorded again on the
+    stream after the speculative pass."""
+    sizes, mapping, status = _encode_batch_args("encode_objects_batch", plan, src, dst, batch, sizes, mapping, status,
+                                                stream)
+    ev = None
+    if phase_event is not None:
+        if not phase_event.cuda_event:
+            raise ValueError("phase_event must have been recorded once (torch creates events lazily)")
+        ev = ctypes.c_void_p(phase_event.cuda_event)
+    _note_unprobed(src)
+    if dst.data_ptr() != src.data_ptr():
+        _note_unprobed(dst)
+    N.check(lib.slime_rs_encode_objects_batch_phased(
+        plan._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+        _stream_handle(plan.device, stream), ev))
+    return mapping, status
+
+
+def resolve_fallbacks_batch(plan: Plan, src: torch.Tensor, dst: torch.Tensor, batch: Batch, sizes,
+                            mapping: torch.Tensor, status: torch.Tensor,
+                            stream: Optional[torch.cuda.Stream] = None) -> int:
+    """Finish the objects of a ragged encode that need MapToGF's random mapping
+    (slime_rs_resolve_fallbacks_batch): mapping[o] is written, only those objects are re-encoded,
+    their status is cleared.  Synchronous; returns how many were fixed."""
+    if mapping is None or status is None:
+        raise ValueError("resolve_fallbacks_batch needs the mapping and status of encode_objects_batch")
+    sizes, mapping, status = _encode_batch_args("resolve_fallbacks_batch", plan, src, dst, batch, sizes, mapping,
+                                                status, stream)
+    n = ctypes.c_int(0)
+    N.check(lib.slime_rs_resolve_fallbacks_batch(
+        plan._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+        _stream_handle(plan.device, stream), ctypes.byref(n)))
+    return n.value
