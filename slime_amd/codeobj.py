@@ -53,15 +53,19 @@ def _symbols(elf: bytes):
             yield name, elf[start: start + st_size]
 
 
+def kernel_codes(path: str, arch: str = "gfx950") -> list[tuple[str, int, str]]:
+    """(mangled name, size in bytes, sha256 of the instruction bytes) of every
+    function symbol with code in every `arch` code object of a library or an
+    object file, in file order."""
+    blob = open(path, "rb").read()
+    return [(name, len(code), hashlib.sha256(code).hexdigest())
+            for co in _gfx_code_objects(blob, arch) for name, code in _symbols(co) if code]
+
+
 def kernel_code_id(lib_path: str, fragments: tuple[str, ...]) -> str | None:
     """sha256[:16] of the machine code of the one kernel whose mangled name
     contains every fragment (None if absent or ambiguous)."""
-    blob = open(lib_path, "rb").read()
-    hits = []
-    for co in _gfx_code_objects(blob):
-        for name, code in _symbols(co):
-            if all(f in name for f in fragments) and code:
-                hits.append(code)
+    hits = [sha for name, _, sha in kernel_codes(lib_path) if all(f in name for f in fragments)]
     if len(hits) != 1:
         return None
-    return hashlib.sha256(hits[0]).hexdigest()[:16]
+    return hits[0][:16]

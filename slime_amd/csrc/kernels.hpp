@@ -289,11 +289,39 @@ struct VerifyLaunch {
 hipError_t launch_verify(const VerifyLaunch& v, hipStream_t stream);
 
 // --- ragged batches (rs_ragged.hip) ------------------------------------------
+// The two sides every ragged launch has.  The batch's: the device tables of
+// ragged_plan.hpp -- one descriptor per object, the unit list and the tail
+// list -- cut by the geometry U, C = ragged::geometry_for_k(k).
+struct RaggedWork {
+  const ragged::Desc* desc = nullptr;
+  const ragged::Unit* units = nullptr;
+  const ragged::Tail* tails = nullptr;
+  uint32_t nunits = 0;
+  uint64_t ntails = 0;
+  uint64_t nobj = 0;  // the batch's objects (verify's result arrays, the encode's per-object steps)
+  int U = 0, C = 0;
+  uint32_t k = 0;
+  bool vec_ok = false;  // 4-byte aligned bases: the 4-columns-per-lane kernels may run
+};
+// The plan's: one plan's device tables (coeff / in_idx / out_idx, `rows` rows)
+// for every object of the batch, or -- table != nullptr -- a plan set's device
+// table (planset_table.hpp), object o taking plan desc[o].reserved[0] of it.
+// The batch was then created planned, with the set's plan count, so every
+// index is below it.
+struct RaggedPlan {
+  const uint32_t* coeff = nullptr;
+  const uint32_t* in_idx = nullptr;
+  const uint32_t* out_idx = nullptr;
+  const uint32_t* table = nullptr;
+  uint32_t rows = 0;
+};
+
 // One matrix application over objects of different lengths: object o's
 // offsets, strides and length come from desc[o], the work from the unit and
-// tail lists (ragged_plan.hpp; all three device tables, cut by the geometry
-// U, C = ragged::geometry_for_k(k)).  For every object and b < L_o:
+// tail lists.  For every object and b < L_o:
 //   out[dst_off + out_idx[i]*dst_shard + b] = sum_j coeff[i][j] * in[src_off + in_idx[j]*src_shard + b]
+// with the one plan (slime_rs_plan_execute_batch) or the object's own plan of
+// a set (slime_rs_planset_execute_batch): that plan's inputs, rows and outputs.
 // k <= 16 with vec_ok runs the 4-columns-per-lane kernel on the dynamic or
 // the static schedule, as launch_apply chooses between them; wider codes and
 // bases that are not 4-byte aligned run one column per lane.  Reads device
@@ -301,40 +329,10 @@ hipError_t launch_verify(const VerifyLaunch& v, hipStream_t stream);
 struct RaggedLaunch {
   const uint32_t* in;
   uint32_t* out;
-  const ragged::Desc* desc;
-  const ragged::Unit* units;
-  const ragged::Tail* tails;
-  uint32_t nunits;
-  uint64_t ntails;
-  int U, C;
-  const uint32_t* coeff;
-  const uint32_t* in_idx;
-  const uint32_t* out_idx;
-  uint32_t rows, k;
-  bool vec_ok;
+  RaggedWork w;
+  RaggedPlan p;
 };
 hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t stream);
-
-// The same launch with a plan per object (slime_rs_planset_execute_batch):
-// desc[o] names plan desc[o].reserved[0] of the set whose device table
-// (planset_table.hpp) is `table`; that plan's inputs, rows and outputs are
-// applied to object o.  The batch was created planned, with the set's plan
-// count, so every index is below it.  Forms, schedules and capture rules are
-// launch_apply_ragged's.
-struct PlannedLaunch {
-  const uint32_t* in;
-  uint32_t* out;
-  const ragged::Desc* desc;
-  const ragged::Unit* units;
-  const ragged::Tail* tails;
-  uint32_t nunits;
-  uint64_t ntails;
-  int U, C;
-  const uint32_t* table;
-  uint32_t k;
-  bool vec_ok;
-};
-hipError_t launch_apply_planned(const PlannedLaunch& a, hipStream_t stream);
 
 // --- ragged verify (rs_verify_ragged.hip) -------------------------------------
 // launch_verify's question asked of a ragged batch: for every object o and row
@@ -343,33 +341,21 @@ hipError_t launch_apply_planned(const PlannedLaunch& a, hipStream_t stream);
 // of row i over the inputs at in + src_off + in_idx[j]*src_shard + b, and
 // first[o*rows + i] = the lowest such column inside the object or UINT64_MAX.
 // Offsets and strides are the descriptors' (uint32 elements).
-//   table == nullptr: one plan (coeff / in_idx / out_idx, `rows` rows) for
-//     every object of the batch;
-//   table != nullptr: a plan set's table, object o checked against plan
-//     desc[o].reserved[0]; `rows` is the set's max_rows (the result arrays' row
-//     stride), rows at or past an object's own plan's keep their initial values.
-// The launch initialises both result arrays (nobj x rows) on the stream with
-// rs_verify_init_kernel whenever nobj > 0, writes nothing else and uses no
+//   one plan: p.rows is the plan's;
+//   a set: object o is checked against its own plan; p.rows is the set's
+//     max_rows (the result arrays' row stride), rows at or past an object's own
+//     plan's keep their initial values.
+// The launch initialises both result arrays (w.nobj x p.rows) on the stream with
+// rs_verify_init_kernel whenever w.nobj > 0, writes nothing else and uses no
 // scratch.  Forms, schedules and capture rules are launch_apply_ragged's; more
 // than 64 rows go in row blocks of 64, one launch (and counter set) each.
 struct RaggedVerifyLaunch {
   const uint32_t* in;
   const uint32_t* cmp;
-  const ragged::Desc* desc;
-  const ragged::Unit* units;
-  const ragged::Tail* tails;
-  uint32_t nunits;
-  uint64_t ntails;
-  int U, C;
-  const uint32_t* coeff = nullptr;
-  const uint32_t* in_idx = nullptr;
-  const uint32_t* out_idx = nullptr;
-  const uint32_t* table = nullptr;
+  RaggedWork w;
+  RaggedPlan p;
   uint64_t* mismatches;
   uint64_t* first;
-  uint64_t nobj;
-  uint32_t rows, k;
-  bool vec_ok;
 };
 hipError_t launch_verify_ragged(const RaggedVerifyLaunch& v, hipStream_t stream);
 // The result arrays' initial state (count 0, first UINT64_MAX) for n entries:
@@ -377,30 +363,19 @@ hipError_t launch_verify_ragged(const RaggedVerifyLaunch& v, hipStream_t stream)
 hipError_t launch_verify_init(uint64_t* mismatches, uint64_t* first, uint64_t n, hipStream_t stream);
 
 // --- ragged byte objects (rs_bytes_ragged.hip) ----------------------------------
-// launch_apply_ragged / launch_apply_planned over stored chunk bytes: a word
-// is big-endian and XOR-ed with mapping[o] (the byte kernels' framing), the
-// descriptors' offsets and strides count 4-byte words of chunk bytes from
-// in / out.  For every object o with work, its plan's rows i and b < L_o:
+// launch_apply_ragged over stored chunk bytes: a word is big-endian and XOR-ed
+// with mapping[o] (the byte kernels' framing), the descriptors' offsets and
+// strides count 4-byte words of chunk bytes from in / out.  For every object o
+// with work, its plan's rows i and b < L_o:
 //   out word = BE(((sum_j coeff[i][j] * (BE(in word) ^ m)) mod p) ^ m), m = mapping[o].
-//   table == nullptr: one plan (coeff / in_idx / out_idx, `rows` rows);
-//   table != nullptr: a plan set's table, object o decoded with plan desc[o].reserved[0].
-// Forms, schedules and capture rules are launch_apply_ragged's.
+// One plan or a set's as RaggedPlan says.  Forms, schedules and capture rules
+// are launch_apply_ragged's.
 struct RaggedBytesLaunch {
   const uint8_t* in;
   uint8_t* out;
-  const ragged::Desc* desc;
-  const ragged::Unit* units;
-  const ragged::Tail* tails;
-  uint32_t nunits;
-  uint64_t ntails;
-  int U, C;
-  const uint32_t* coeff = nullptr;
-  const uint32_t* in_idx = nullptr;
-  const uint32_t* out_idx = nullptr;
-  const uint32_t* table = nullptr;
+  RaggedWork w;
+  RaggedPlan p;
   const uint32_t* mapping;  // nobj mapping values (device)
-  uint32_t rows, k;
-  bool vec_ok;
 };
 hipError_t launch_decode_bytes_ragged(const RaggedBytesLaunch& a, hipStream_t stream);
 
@@ -410,22 +385,11 @@ hipError_t launch_decode_bytes_ragged(const RaggedBytesLaunch& a, hipStream_t st
 struct RaggedBytesVerifyLaunch {
   const uint8_t* in;
   const uint8_t* cmp;
-  const ragged::Desc* desc;
-  const ragged::Unit* units;
-  const ragged::Tail* tails;
-  uint32_t nunits;
-  uint64_t ntails;
-  int U, C;
-  const uint32_t* coeff = nullptr;
-  const uint32_t* in_idx = nullptr;
-  const uint32_t* out_idx = nullptr;
-  const uint32_t* table = nullptr;
+  RaggedWork w;
+  RaggedPlan p;
   const uint32_t* mapping;  // nobj mapping values (device)
   uint64_t* mismatches;
   uint64_t* first;
-  uint64_t nobj;
-  uint32_t rows, k;
-  bool vec_ok;
 };
 hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStream_t stream);
 
@@ -433,7 +397,8 @@ hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStrea
 // The fused byte encode over a ragged batch: object o of sizes[o] bytes, its k
 // data chunks read (and their tails rewritten) through the descriptor's src
 // side, the plan's rows written through its dst side.  The plan reads inputs
-// 0 .. k-1 in that order (the host checks it), so no in_idx.  A call is the
+// 0 .. k-1 in that order (the host checks it), so p.in_idx is not read; the
+// edge items come from the descriptors, so neither is w.tails.  A call is the
 // steps below in order on one stream; slime_rs_resolve_fallbacks_batch marks
 // objects kRaggedEncodePending itself and runs Pass1 and Clear.  Forms,
 // schedules and capture rules are launch_decode_bytes_ragged's; each dynamic
@@ -449,19 +414,12 @@ enum class RaggedEncodeStep {
 struct RaggedEncodeLaunch {
   uint8_t* src;
   uint8_t* dst;
-  const ragged::Desc* desc;
-  const ragged::Unit* units;
-  uint32_t nunits;
-  uint32_t nobj;
-  bool has_work;  // some object has columns (units or tails)
-  int U, C;
-  const uint32_t* coeff;
-  const uint32_t* out_idx;
+  RaggedWork w;
+  RaggedPlan p;           // one plan
+  bool has_work;          // some object has columns (units or tails)
   const uint64_t* sizes;  // nobj object sizes in bytes (device)
   uint32_t* mapping;      // nobj words (device)
   uint32_t* status;       // nobj words (device)
-  uint32_t rows, k;
-  bool vec_ok;
 };
 hipError_t launch_encode_bytes_ragged(const RaggedEncodeLaunch& a, RaggedEncodeStep step, hipStream_t stream);
 

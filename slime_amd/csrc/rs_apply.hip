@@ -28,6 +28,7 @@
 
 #include "kernels.hpp"
 #include "rs_apply_kernel.hpp"
+#include "rs_ragged_launch.hpp"  // with_k
 
 namespace slime {
 
@@ -514,25 +515,8 @@ hipError_t launch_apply(const ApplyLaunch& a, hipStream_t s) {
   (void)hipGetLastError();  // report only this launch's error, not one left on the thread
   if (a.nobj == 0 || a.ncols == 0 || a.rows == 0) return hipSuccess;
   if (mfma_eligible(a)) return launch_apply_mfma(a, s);  // wide codes on the matrix cores
-  switch (a.k) {
-    case 1: return dispatch_vec<1>(a, s);
-    case 2: return dispatch_vec<2>(a, s);
-    case 3: return dispatch_vec<3>(a, s);
-    case 4: return dispatch_vec<4>(a, s);
-    case 5: return dispatch_vec<5>(a, s);
-    case 6: return dispatch_vec<6>(a, s);
-    case 7: return dispatch_vec<7>(a, s);
-    case 8: return dispatch_vec<8>(a, s);
-    case 9: return dispatch_vec<9>(a, s);
-    case 10: return dispatch_vec<10>(a, s);
-    case 11: return dispatch_vec<11>(a, s);
-    case 12: return dispatch_vec<12>(a, s);
-    case 13: return dispatch_vec<13>(a, s);
-    case 14: return dispatch_vec<14>(a, s);
-    case 15: return dispatch_vec<15>(a, s);
-    case 16: return dispatch_vec<16>(a, s);
-    default: return a.vec_ok ? launch_wide(a, s) : launch_k<0, false>(a, s);
-  }
+  if (a.k < 1 || a.k > 16) return a.vec_ok ? launch_wide(a, s) : launch_k<0, false>(a, s);
+  return ragged::with_k(a.k, [&](auto kc) { return dispatch_vec<decltype(kc)::value>(a, s); });
 }
 
 }  // namespace slime

@@ -43,12 +43,11 @@
 // Only plain C++ vector stores and vector atomics write memory.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "encode_edge.hpp"
 #include "kernels.hpp"
 #include "rs_apply_kernel.hpp"
 #include "rs_bytes_kernel.hpp"  // load_raw_tile, rows_tile, be, Flags, packed_word
+#include "rs_ragged_launch.hpp"
 #include "rs_ragged_walk.hpp"
 
 namespace slime {
@@ -330,102 +329,62 @@ __global__ void encode_clear_kernel(uint32_t* __restrict__ status, uint32_t nobj
 namespace {
 
 using apply::kBlock;
-constexpr uint64_t kQueueBlocks = 256;  // one block per CU, as the ragged apply launch
 
-// Blocks of a pass: one wave per unit up to `full`, and enough lanes for the
-// edge items of a batch of many short objects (rs_bytes_ragged.hip, ragged_blocks).
-uint64_t encode_blocks(uint64_t full, uint64_t nunits, uint64_t nedge) {
-  const uint64_t by_units = queue_blocks(full, nunits);
-  const uint64_t by_edges = (nedge + kBlock - 1) / kBlock;
-  const uint64_t want = by_edges < full ? by_edges : full;
-  return by_units > want ? by_units : want;
-}
+// The per-lane items of a pass are its edge columns, not the tail list.
+uint64_t edge_items(const RaggedEncodeLaunch& a) { return a.w.nobj * edge::edge_columns_max(a.w.k); }
 
-uint64_t edge_items(const RaggedEncodeLaunch& a) { return (uint64_t)a.nobj * edge::edge_columns_max(a.k); }
+#define SLIME_BENCODE_ARGS(a, pass)                                                                              \
+  (a).src, (a).dst, (a).w.desc, (a).w.units, (a).p.coeff, (a).p.out_idx, (a).sizes, (a).mapping, (a).status,      \
+      (a).w.nunits, (uint32_t)(a).w.nobj, (a).p.rows, (a).w.k, (uint32_t)(pass)
 
-// f(std::integral_constant<int, K>) for the launch's k in 1 ... 16.
-template <class F>
-hipError_t with_k(uint32_t k, F&& f) {
-  switch (k) {
-#define SLIME_K(n) \
-  case n: return f(std::integral_constant<int, n>{});
-    SLIME_K(1) SLIME_K(2) SLIME_K(3) SLIME_K(4) SLIME_K(5) SLIME_K(6) SLIME_K(7) SLIME_K(8)
-    SLIME_K(9) SLIME_K(10) SLIME_K(11) SLIME_K(12) SLIME_K(13) SLIME_K(14) SLIME_K(15)
-#undef SLIME_K
-    default: return f(std::integral_constant<int, 16>{});
-  }
-}
-
-#define SLIME_BENCODE_ARGS(a, pass)                                                                          \
-  (a).src, (a).dst, (a).desc, (a).units, (a).coeff, (a).out_idx, (a).sizes, (a).mapping, (a).status, (a).nunits, \
-      (a).nobj, (a).rows, (a).k, (uint32_t)(pass)
-
-// The grids and the choice between the schedules are launch_decode_bytes_ragged's.
-template <int K, bool PIPE>
-hipError_t pass_static(const RaggedEncodeLaunch& a, int pass, hipStream_t s) {
-  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
-  const uint64_t blocks = encode_blocks(K <= 12 ? 256 : 1024, a.nunits, edge_items(a));
-  hipLaunchKernelGGL((bytes_ragged_encode::rs_encode_ragged_kernel<K, U, C, kQueueCounters, false, PIPE>),
-                     dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_BENCODE_ARGS(a, pass), nullptr);
-  return hipGetLastError();
-}
-
+// The grids are launch_decode_bytes_ragged's.
 template <int K>
-hipError_t pass_dispatch(const RaggedEncodeLaunch& a, int pass, hipStream_t s) {
+hipError_t pass_vectors(const RaggedEncodeLaunch& a, int pass, hipStream_t s) {
   constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
-  if (!pipelined_kernels()) return pass_static<K, false>(a, pass, s);
-  // The dynamic schedule has nothing to balance over one block's units (queue_spread, kernels.hpp).
-  if (queue_allowed(s) && a.nunits > tiny_queue_units()) {
-    bool launched = false;
-    const uint64_t blocks = encode_blocks(kQueueBlocks, a.nunits, edge_items(a));
-    const hipError_t e = with_tickets(
-        s,
-        [&](uint32_t* set) {
-          hipLaunchKernelGGL((bytes_ragged_encode::rs_encode_ragged_kernel<K, U, C, kQueueCounters, true, true>),
-                             dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_BENCODE_ARGS(a, pass), set);
-          return hipGetLastError();
-        },
-        &launched);
-    if (launched || e != hipSuccess) return e;
-  }
-  return pass_static<K, true>(a, pass, s);
+  return ragged::launch_scheduled(
+      s, a.w.nunits, edge_items(a), K <= 12 ? 256 : 1024, [&](auto dyn, auto pipe, uint64_t blocks, uint32_t* set) {
+        constexpr bool DYN = decltype(dyn)::value, PIPE = decltype(pipe)::value;
+        hipLaunchKernelGGL((bytes_ragged_encode::rs_encode_ragged_kernel<K, U, C, kQueueCounters, DYN, PIPE>),
+                           dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_BENCODE_ARGS(a, pass), set);
+        return hipGetLastError();
+      });
 }
 
 hipError_t pass_columns(const RaggedEncodeLaunch& a, int pass, hipStream_t s) {
-  const uint64_t blocks = encode_blocks(1024, a.nunits, edge_items(a));
+  const uint64_t blocks = ragged::ragged_blocks(1024, a.w.nunits, edge_items(a));
   hipLaunchKernelGGL(bytes_ragged_encode::rs_encode_ragged_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
-                     SLIME_BENCODE_ARGS(a, pass), 256u * (uint32_t)a.U, (uint32_t)a.C);
+                     SLIME_BENCODE_ARGS(a, pass), 256u * (uint32_t)a.w.U, (uint32_t)a.w.C);
   return hipGetLastError();
 }
 
 #undef SLIME_BENCODE_ARGS
 
 hipError_t encode_pass(const RaggedEncodeLaunch& a, int pass, hipStream_t s) {
-  if (a.k > 16 || !a.vec_ok) return pass_columns(a, pass, s);
+  if (a.w.k > 16 || !a.w.vec_ok) return pass_columns(a, pass, s);
   // The vector kernels are instantiated with the geometry of their K: the tables must be cut by it.
-  if (a.U != ragged::unroll_for_k((int)a.k) || a.C != ragged::unit_tiles_for_k((int)a.k)) return hipErrorInvalidValue;
-  return with_k(a.k, [&](auto kc) { return pass_dispatch<decltype(kc)::value>(a, pass, s); });
+  if (a.w.U != ragged::unroll_for_k((int)a.w.k) || a.w.C != ragged::unit_tiles_for_k((int)a.w.k))
+    return hipErrorInvalidValue;
+  return ragged::with_k(a.w.k, [&](auto kc) { return pass_vectors<decltype(kc)::value>(a, pass, s); });
 }
 
 }  // namespace
 
 hipError_t launch_encode_bytes_ragged(const RaggedEncodeLaunch& a, RaggedEncodeStep step, hipStream_t s) {
   (void)hipGetLastError();  // report only this launch's error, not one left on the thread
-  if (a.nobj == 0) return hipSuccess;
-  const dim3 per_obj((a.nobj + 255) / 256);
+  if (a.w.nobj == 0) return hipSuccess;
+  const uint32_t nobj = (uint32_t)a.w.nobj;
+  const dim3 per_obj((nobj + 255) / 256);
   switch (step) {
     case RaggedEncodeStep::Init:
-      hipLaunchKernelGGL(bytes_ragged_encode::encode_init_kernel, per_obj, dim3(256), 0, s, a.mapping, a.status,
-                         a.nobj);
+      hipLaunchKernelGGL(bytes_ragged_encode::encode_init_kernel, per_obj, dim3(256), 0, s, a.mapping, a.status, nobj);
       return hipGetLastError();
     case RaggedEncodeStep::Pass0: return a.has_work ? encode_pass(a, 0, s) : hipSuccess;
     case RaggedEncodeStep::Select:
-      hipLaunchKernelGGL(bytes_ragged_encode::encode_select_kernel, per_obj, dim3(256), 0, s, a.mapping, a.status,
-                         a.nobj);
+      hipLaunchKernelGGL(bytes_ragged_encode::encode_select_kernel, per_obj, dim3(256), 0, s, a.mapping, a.status, nobj);
       return hipGetLastError();
     case RaggedEncodeStep::Pass1: return a.has_work ? encode_pass(a, 1, s) : hipSuccess;
     case RaggedEncodeStep::Clear:
-      hipLaunchKernelGGL(bytes_ragged_encode::encode_clear_kernel, per_obj, dim3(256), 0, s, a.status, a.nobj);
+      hipLaunchKernelGGL(bytes_ragged_encode::encode_clear_kernel, per_obj, dim3(256), 0, s, a.status, nobj);
       return hipGetLastError();
   }
   return hipErrorInvalidValue;

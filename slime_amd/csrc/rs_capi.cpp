@@ -597,32 +597,73 @@ int slime_rs_batch_destroy(slime_rs_batch_t batch) {
   return 0;
 }
 
-int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
-                                void* stream) {
-  if (!plan) return fail(Status::InvalidArg, "plan_execute_batch: null plan");
-  if (!batch) return fail(Status::InvalidArg, "plan_execute_batch: null batch");
+// What every batch entry point checks first, in this order; `what` names the entry point.
+static int check_batch_plan(const char* what, const slime_rs_plan* plan, const slime_rs_batch* batch) {
+  if (!plan) return fail(Status::InvalidArg, std::string(what) + ": null plan");
+  if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
   if (plan->k != batch->k || plan->device != batch->device)
-    return fail(Status::InvalidArg, "plan_execute_batch: the batch was created for k = " + std::to_string(batch->k) +
+    return fail(Status::InvalidArg, std::string(what) + ": the batch was created for k = " + std::to_string(batch->k) +
                                         " on device " + std::to_string(batch->device) + ", the plan has k = " +
                                         std::to_string(plan->k) + " on device " + std::to_string(plan->device));
-  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  return 0;
+}
+
+static int check_batch_set(const char* what, const slime_rs_planset* set, const slime_rs_batch* batch) {
+  if (!set) return fail(Status::InvalidArg, std::string(what) + ": null set");
+  if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
+  if (!batch->planned)
+    return fail(Status::InvalidArg, std::string(what) + ": the batch carries no plan indices "
+                                                        "(create it with slime_rs_batch_create_planned)");
+  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
+    return fail(Status::InvalidArg, std::string(what) + ": the batch was created for " + std::to_string(batch->nplans) +
+                                        " plans of k = " + std::to_string(batch->k) + " on device " +
+                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
+                                        " plans of k = " + std::to_string(set->k) + " on device " +
+                                        std::to_string(set->device));
+  return 0;
+}
+
+static bool batch_has_work(const slime_rs_batch* batch) { return batch->counts.units != 0 || batch->counts.tails != 0; }
+
+// The batch's side of a ragged launch over the buffers a and b (the vector
+// kernels need both 4-byte aligned, as slime_rs_plan_execute).
+static RaggedWork batch_work(const slime_rs_batch* batch, const void* a, const void* b) {
+  RaggedWork w;
+  w.desc = batch->d_desc;
+  w.units = batch->d_units;
+  w.tails = batch->d_tails;
+  w.nunits = (uint32_t)batch->counts.units;
+  w.ntails = batch->counts.tails;
+  w.nobj = batch->counts.nobj;
+  w.U = batch->g.U;
+  w.C = batch->g.C;
+  w.k = batch->k;
+  w.vec_ok = aligned4(a) && aligned4(b);
+  return w;
+}
+
+// The plan's side: one plan for every object, or a set's table (rows: the
+// verify launches set the result arrays' row stride themselves).
+static RaggedPlan plan_side(const slime_rs_plan* plan) {
+  RaggedPlan p;
+  p.coeff = plan->d_coeff;
+  p.in_idx = plan->d_in_idx;
+  p.out_idx = plan->d_out_idx;
+  p.rows = plan->rows;
+  return p;
+}
+static RaggedPlan plan_side(const slime_rs_planset* set) {
+  RaggedPlan p;
+  p.table = set->d_table;
+  return p;
+}
+
+int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
+                                void* stream) {
+  if (int rc = check_batch_plan("plan_execute_batch", plan, batch)) return rc;
+  if (!batch_has_work(batch)) return 0;  // an empty batch
   if (!src || !dst) return fail(Status::InvalidArg, "plan_execute_batch: null buffer");
-  RaggedLaunch a;
-  a.in = src;
-  a.out = dst;
-  a.desc = batch->d_desc;
-  a.units = batch->d_units;
-  a.tails = batch->d_tails;
-  a.nunits = (uint32_t)batch->counts.units;
-  a.ntails = batch->counts.tails;
-  a.U = batch->g.U;
-  a.C = batch->g.C;
-  a.coeff = plan->d_coeff;
-  a.in_idx = plan->d_in_idx;
-  a.out_idx = plan->d_out_idx;
-  a.rows = plan->rows;
-  a.k = plan->k;
-  a.vec_ok = aligned4(src) && aligned4(dst);  // as slime_rs_plan_execute
+  const RaggedLaunch a{src, dst, batch_work(batch, src, dst), plan_side(plan)};
   plan->executed.store(true, std::memory_order_relaxed);
   DeviceScope ds(plan->device);
   HIP_TRY(launch_apply_ragged(a, (hipStream_t)stream));
@@ -696,34 +737,12 @@ int slime_rs_planset_destroy(slime_rs_planset_t set) {
 
 int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
                                    void* stream) {
-  if (!set) return fail(Status::InvalidArg, "planset_execute_batch: null set");
-  if (!batch) return fail(Status::InvalidArg, "planset_execute_batch: null batch");
-  if (!batch->planned)
-    return fail(Status::InvalidArg, "planset_execute_batch: the batch carries no plan indices "
-                                    "(create it with slime_rs_batch_create_planned)");
-  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
-    return fail(Status::InvalidArg, "planset_execute_batch: the batch was created for " + std::to_string(batch->nplans) +
-                                        " plans of k = " + std::to_string(batch->k) + " on device " +
-                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
-                                        " plans of k = " + std::to_string(set->k) + " on device " +
-                                        std::to_string(set->device));
-  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (int rc = check_batch_set("planset_execute_batch", set, batch)) return rc;
+  if (!batch_has_work(batch)) return 0;  // an empty batch
   if (!src || !dst) return fail(Status::InvalidArg, "planset_execute_batch: null buffer");
-  PlannedLaunch a;
-  a.in = src;
-  a.out = dst;
-  a.desc = batch->d_desc;
-  a.units = batch->d_units;
-  a.tails = batch->d_tails;
-  a.nunits = (uint32_t)batch->counts.units;
-  a.ntails = batch->counts.tails;
-  a.U = batch->g.U;
-  a.C = batch->g.C;
-  a.table = set->d_table;
-  a.k = set->k;
-  a.vec_ok = aligned4(src) && aligned4(dst);
+  const RaggedLaunch a{src, dst, batch_work(batch, src, dst), plan_side(set)};
   DeviceScope ds(set->device);
-  HIP_TRY(launch_apply_planned(a, (hipStream_t)stream));
+  HIP_TRY(launch_apply_ragged(a, (hipStream_t)stream));
   return 0;
 }
 
@@ -756,43 +775,20 @@ int slime_rs_plan_verify(slime_rs_plan_t plan, const uint32_t* src, slime_rs_lay
 
 // ---- ragged verify (rs_verify_ragged.hip) ------------------------------------------
 
-// The batch's side of a ragged verify launch.
-static RaggedVerifyLaunch verify_batch_launch(const slime_rs_batch* batch, const uint32_t* src, const uint32_t* cmp,
-                                              uint64_t* mismatches, uint64_t* first) {
-  RaggedVerifyLaunch v{};
-  v.in = src;
-  v.cmp = cmp;
-  v.desc = batch->d_desc;
-  v.units = batch->d_units;
-  v.tails = batch->d_tails;
-  v.nunits = (uint32_t)batch->counts.units;
-  v.ntails = batch->counts.tails;
-  v.U = batch->g.U;
-  v.C = batch->g.C;
-  v.mismatches = mismatches;
-  v.first = first;
-  v.nobj = batch->counts.nobj;
-  v.k = batch->k;
-  v.vec_ok = aligned4(src) && aligned4(cmp);  // as slime_rs_plan_verify
-  return v;
+// What both verify forms check next, symbols or bytes (a null mapping is the byte entry points' own check).
+static int check_verify_batch(const char* what, const void* src, const void* cmp, const uint64_t* mismatches,
+                              const uint64_t* first) {
+  if (!mismatches || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  return 0;
 }
 
 int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, const uint32_t* cmp,
                                uint64_t* mismatches, uint64_t* first, void* stream) {
-  if (!plan) return fail(Status::InvalidArg, "plan_verify_batch: null plan");
-  if (!batch) return fail(Status::InvalidArg, "plan_verify_batch: null batch");
-  if (plan->k != batch->k || plan->device != batch->device)
-    return fail(Status::InvalidArg, "plan_verify_batch: the batch was created for k = " + std::to_string(batch->k) +
-                                        " on device " + std::to_string(batch->device) + ", the plan has k = " +
-                                        std::to_string(plan->k) + " on device " + std::to_string(plan->device));
-  if (!mismatches || !first) return fail(Status::InvalidArg, "plan_verify_batch: null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, "plan_verify_batch: null buffer");
+  if (int rc = check_batch_plan("plan_verify_batch", plan, batch)) return rc;
+  if (int rc = check_verify_batch("plan_verify_batch", src, cmp, mismatches, first)) return rc;
   if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  RaggedVerifyLaunch v = verify_batch_launch(batch, src, cmp, mismatches, first);
-  v.coeff = plan->d_coeff;
-  v.in_idx = plan->d_in_idx;
-  v.out_idx = plan->d_out_idx;
-  v.rows = plan->rows;
+  const RaggedVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), mismatches, first};
   // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
   plan->executed.store(true, std::memory_order_relaxed);
   DeviceScope ds(plan->device);
@@ -802,23 +798,11 @@ int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, con
 
 int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src,
                                   const uint32_t* cmp, uint64_t* mismatches, uint64_t* first, void* stream) {
-  if (!set) return fail(Status::InvalidArg, "planset_verify_batch: null set");
-  if (!batch) return fail(Status::InvalidArg, "planset_verify_batch: null batch");
-  if (!batch->planned)
-    return fail(Status::InvalidArg, "planset_verify_batch: the batch carries no plan indices "
-                                    "(create it with slime_rs_batch_create_planned)");
-  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
-    return fail(Status::InvalidArg, "planset_verify_batch: the batch was created for " + std::to_string(batch->nplans) +
-                                        " plans of k = " + std::to_string(batch->k) + " on device " +
-                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
-                                        " plans of k = " + std::to_string(set->k) + " on device " +
-                                        std::to_string(set->device));
-  if (!mismatches || !first) return fail(Status::InvalidArg, "planset_verify_batch: null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, "planset_verify_batch: null buffer");
+  if (int rc = check_batch_set("planset_verify_batch", set, batch)) return rc;
+  if (int rc = check_verify_batch("planset_verify_batch", src, cmp, mismatches, first)) return rc;
   if (batch->counts.nobj == 0) return 0;
-  RaggedVerifyLaunch v = verify_batch_launch(batch, src, cmp, mismatches, first);
-  v.table = set->d_table;
-  v.rows = set->max_rows;  // the result arrays' row stride
+  RaggedVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), mismatches, first};
+  v.p.rows = set->max_rows;  // the result arrays' row stride
   DeviceScope ds(set->device);
   HIP_TRY(launch_verify_ragged(v, (hipStream_t)stream));
   return 0;
@@ -827,83 +811,13 @@ int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch
 // ---- ragged byte objects (rs_bytes_ragged.hip) --------------------------------------
 // The four ragged launches over stored chunk bytes; validation as their symbol twins.
 
-// The checks both plan forms share; `what` names the entry point.
-static int check_batch_plan(const char* what, const slime_rs_plan* plan, const slime_rs_batch* batch) {
-  if (!plan) return fail(Status::InvalidArg, std::string(what) + ": null plan");
-  if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
-  if (plan->k != batch->k || plan->device != batch->device)
-    return fail(Status::InvalidArg, std::string(what) + ": the batch was created for k = " + std::to_string(batch->k) +
-                                        " on device " + std::to_string(batch->device) + ", the plan has k = " +
-                                        std::to_string(plan->k) + " on device " + std::to_string(plan->device));
-  return 0;
-}
-
-static int check_batch_set(const char* what, const slime_rs_planset* set, const slime_rs_batch* batch) {
-  if (!set) return fail(Status::InvalidArg, std::string(what) + ": null set");
-  if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
-  if (!batch->planned)
-    return fail(Status::InvalidArg, std::string(what) + ": the batch carries no plan indices "
-                                                        "(create it with slime_rs_batch_create_planned)");
-  if (set->k != batch->k || set->device != batch->device || set->nplans != batch->nplans)
-    return fail(Status::InvalidArg, std::string(what) + ": the batch was created for " + std::to_string(batch->nplans) +
-                                        " plans of k = " + std::to_string(batch->k) + " on device " +
-                                        std::to_string(batch->device) + ", the set has " + std::to_string(set->nplans) +
-                                        " plans of k = " + std::to_string(set->k) + " on device " +
-                                        std::to_string(set->device));
-  return 0;
-}
-
-static RaggedBytesLaunch decode_batch_launch(const slime_rs_batch* batch, const uint8_t* src, uint8_t* dst,
-                                             const uint32_t* mapping) {
-  RaggedBytesLaunch a{};
-  a.in = src;
-  a.out = dst;
-  a.desc = batch->d_desc;
-  a.units = batch->d_units;
-  a.tails = batch->d_tails;
-  a.nunits = (uint32_t)batch->counts.units;
-  a.ntails = batch->counts.tails;
-  a.U = batch->g.U;
-  a.C = batch->g.C;
-  a.mapping = mapping;
-  a.k = batch->k;
-  a.vec_ok = aligned4(src) && aligned4(dst);
-  return a;
-}
-
-static RaggedBytesVerifyLaunch verify_objects_launch(const slime_rs_batch* batch, const uint8_t* src,
-                                                     const uint8_t* cmp, const uint32_t* mapping,
-                                                     uint64_t* mismatches, uint64_t* first) {
-  RaggedBytesVerifyLaunch v{};
-  v.in = src;
-  v.cmp = cmp;
-  v.desc = batch->d_desc;
-  v.units = batch->d_units;
-  v.tails = batch->d_tails;
-  v.nunits = (uint32_t)batch->counts.units;
-  v.ntails = batch->counts.tails;
-  v.U = batch->g.U;
-  v.C = batch->g.C;
-  v.mapping = mapping;
-  v.mismatches = mismatches;
-  v.first = first;
-  v.nobj = batch->counts.nobj;
-  v.k = batch->k;
-  v.vec_ok = aligned4(src) && aligned4(cmp);
-  return v;
-}
-
 int slime_rs_decode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src, uint8_t* dst,
                                   const uint32_t* mapping, void* stream) {
   if (int rc = check_batch_plan("decode_objects_batch", plan, batch)) return rc;
-  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (!batch_has_work(batch)) return 0;  // an empty batch
   if (!src || !dst) return fail(Status::InvalidArg, "decode_objects_batch: null buffer");
   if (!mapping) return fail(Status::InvalidArg, "decode_objects_batch: null mapping");
-  RaggedBytesLaunch a = decode_batch_launch(batch, src, dst, mapping);
-  a.coeff = plan->d_coeff;
-  a.in_idx = plan->d_in_idx;
-  a.out_idx = plan->d_out_idx;
-  a.rows = plan->rows;
+  const RaggedBytesLaunch a{src, dst, batch_work(batch, src, dst), plan_side(plan), mapping};
   plan->executed.store(true, std::memory_order_relaxed);
   DeviceScope ds(plan->device);
   HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
@@ -913,11 +827,10 @@ int slime_rs_decode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, 
 int slime_rs_planset_decode_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
                                           uint8_t* dst, const uint32_t* mapping, void* stream) {
   if (int rc = check_batch_set("planset_decode_objects_batch", set, batch)) return rc;
-  if (batch->counts.units == 0 && batch->counts.tails == 0) return 0;  // an empty batch
+  if (!batch_has_work(batch)) return 0;  // an empty batch
   if (!src || !dst) return fail(Status::InvalidArg, "planset_decode_objects_batch: null buffer");
   if (!mapping) return fail(Status::InvalidArg, "planset_decode_objects_batch: null mapping");
-  RaggedBytesLaunch a = decode_batch_launch(batch, src, dst, mapping);
-  a.table = set->d_table;
+  const RaggedBytesLaunch a{src, dst, batch_work(batch, src, dst), plan_side(set), mapping};
   DeviceScope ds(set->device);
   HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
   return 0;
@@ -927,17 +840,11 @@ int slime_rs_verify_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, 
                                   const uint8_t* cmp, const uint32_t* mapping, uint64_t* mismatches, uint64_t* first,
                                   void* stream) {
   if (int rc = check_batch_plan("verify_objects_batch", plan, batch)) return rc;
-  if (!mismatches || !first) return fail(Status::InvalidArg, "verify_objects_batch: null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, "verify_objects_batch: null buffer");
+  if (int rc = check_verify_batch("verify_objects_batch", src, cmp, mismatches, first)) return rc;
   if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
   // An empty batch launches only the initialisation, which reads no mapping.
-  if (!mapping && (batch->counts.units != 0 || batch->counts.tails != 0))
-    return fail(Status::InvalidArg, "verify_objects_batch: null mapping");
-  RaggedBytesVerifyLaunch v = verify_objects_launch(batch, src, cmp, mapping, mismatches, first);
-  v.coeff = plan->d_coeff;
-  v.in_idx = plan->d_in_idx;
-  v.out_idx = plan->d_out_idx;
-  v.rows = plan->rows;
+  if (!mapping && batch_has_work(batch)) return fail(Status::InvalidArg, "verify_objects_batch: null mapping");
+  const RaggedBytesVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), mapping, mismatches, first};
   // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
   plan->executed.store(true, std::memory_order_relaxed);
   DeviceScope ds(plan->device);
@@ -949,15 +856,12 @@ int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch
                                           const uint8_t* cmp, const uint32_t* mapping, uint64_t* mismatches,
                                           uint64_t* first, void* stream) {
   if (int rc = check_batch_set("planset_verify_objects_batch", set, batch)) return rc;
-  if (!mismatches || !first) return fail(Status::InvalidArg, "planset_verify_objects_batch: null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, "planset_verify_objects_batch: null buffer");
+  if (int rc = check_verify_batch("planset_verify_objects_batch", src, cmp, mismatches, first)) return rc;
   if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
   // An empty batch launches only the initialisation, which reads no mapping.
-  if (!mapping && (batch->counts.units != 0 || batch->counts.tails != 0))
-    return fail(Status::InvalidArg, "planset_verify_objects_batch: null mapping");
-  RaggedBytesVerifyLaunch v = verify_objects_launch(batch, src, cmp, mapping, mismatches, first);
-  v.table = set->d_table;
-  v.rows = set->max_rows;  // the result arrays' row stride
+  if (!mapping && batch_has_work(batch)) return fail(Status::InvalidArg, "planset_verify_objects_batch: null mapping");
+  RaggedBytesVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), mapping, mismatches, first};
+  v.p.rows = set->max_rows;  // the result arrays' row stride
   DeviceScope ds(set->device);
   HIP_TRY(launch_verify_bytes_ragged(v, (hipStream_t)stream));
   return 0;
@@ -1266,27 +1170,10 @@ static int encode_batch_launch(const char* what, slime_rs_plan* plan, const slim
     return fail(Status::InvalidArg, std::string(what) + ": the plan must read inputs 0..k-1 in that order "
                                                         "(slime_rs_plan_encode): padding depends on a chunk's position");
   if (!mapping || !status) return fail(Status::InvalidArg, std::string(what) + ": null mapping/status");
-  const bool work = batch->counts.units != 0 || batch->counts.tails != 0;
+  const bool work = batch_has_work(batch);
   if (work && (!src || !dst)) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
   if (work && !sizes) return fail(Status::InvalidArg, std::string(what) + ": null sizes");
-  *a = RaggedEncodeLaunch{};
-  a->src = src;
-  a->dst = dst;
-  a->desc = batch->d_desc;
-  a->units = batch->d_units;
-  a->nunits = (uint32_t)batch->counts.units;
-  a->nobj = (uint32_t)batch->counts.nobj;
-  a->has_work = work;
-  a->U = batch->g.U;
-  a->C = batch->g.C;
-  a->coeff = plan->d_coeff;
-  a->out_idx = plan->d_out_idx;
-  a->sizes = sizes;
-  a->mapping = mapping;
-  a->status = status;
-  a->rows = plan->rows;
-  a->k = plan->k;
-  a->vec_ok = aligned4(src) && aligned4(dst);
+  *a = RaggedEncodeLaunch{src, dst, batch_work(batch, src, dst), plan_side(plan), work, sizes, mapping, status};
   return 0;
 }
 
@@ -1295,7 +1182,7 @@ int slime_rs_encode_objects_batch_phased(slime_rs_plan_t plan, slime_rs_batch_t 
                                          void* phase_event) {
   RaggedEncodeLaunch a;
   if (int rc = encode_batch_launch("encode_objects_batch", plan, batch, src, dst, sizes, mapping, status, &a)) return rc;
-  if (a.nobj == 0) return 0;  // nothing to initialise, nothing to launch
+  if (a.w.nobj == 0) return 0;  // nothing to initialise, nothing to launch
   hipStream_t s = (hipStream_t)stream;
   DeviceScope ds(plan->device);
   HIP_TRY(launch_encode_bytes_ragged(a, RaggedEncodeStep::Init, s));
@@ -1321,10 +1208,10 @@ int slime_rs_resolve_fallbacks_batch(slime_rs_plan_t plan, slime_rs_batch_t batc
   RaggedEncodeLaunch a;
   if (int rc = encode_batch_launch("resolve_fallbacks_batch", plan, batch, src, dst, sizes, mapping, status, &a))
     return rc;
-  if (a.nobj == 0 || !a.has_work) return 0;
+  if (a.w.nobj == 0 || !a.has_work) return 0;
   hipStream_t s = (hipStream_t)stream;
   DeviceScope ds(plan->device);
-  const uint64_t nobj = a.nobj;
+  const uint64_t nobj = a.w.nobj;
   std::vector<uint32_t> st(nobj);
   HIP_TRY(hipMemcpyAsync(st.data(), status, nobj * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

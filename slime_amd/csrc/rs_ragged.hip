@@ -48,7 +48,8 @@
 #include "kernels.hpp"
 #include "planset_table.hpp"
 #include "rs_apply_kernel.hpp"
-#include "rs_ragged_walk.hpp"  // UnitWalk, load_desc, load_plan: shared with rs_verify_ragged.hip
+#include "rs_ragged_launch.hpp"  // the grid, with_k and the choice between the schedules
+#include "rs_ragged_walk.hpp"    // UnitWalk, load_desc, load_plan: shared with rs_verify_ragged.hip
 
 namespace slime {
 namespace ragged {
@@ -299,155 +300,59 @@ namespace {
 using apply::kBlock;
 constexpr bool kNtLoads = true;
 constexpr bool kNtStores = true;
-constexpr uint64_t kQueueBlocks = 256;  // one block per CU, as launch_queue (rs_apply.hip)
 
-// Blocks of a ragged launch: one wave per unit up to `full` (queue_blocks),
-// and enough lanes for the tail items of a batch of many short objects.
-template <class Launch>  // RaggedLaunch or PlannedLaunch
-uint64_t ragged_blocks(uint64_t full, const Launch& a) {
-  const uint64_t by_units = queue_blocks(full, a.nunits);
-  const uint64_t by_tails = (a.ntails + kBlock - 1) / kBlock;
-  const uint64_t want = by_tails < full ? by_tails : full;
-  return by_units > want ? by_units : want;
-}
+#define SLIME_RAGGED_ARGS(a)                                                                                  \
+  (a).in, (a).out, (a).w.desc, (a).w.units, (a).w.tails, (a).p.coeff, (a).p.in_idx, (a).p.out_idx, (a).w.nunits, \
+      (a).w.ntails, (a).p.rows, (a).w.k
+#define SLIME_PLANNED_ARGS(a) \
+  (a).in, (a).out, (a).w.desc, (a).w.units, (a).w.tails, (a).p.table, (a).w.nunits, (a).w.ntails, (a).w.k
 
-#define SLIME_RAGGED_ARGS(a) \
-  (a).in, (a).out, (a).desc, (a).units, (a).tails, (a).coeff, (a).in_idx, (a).out_idx, (a).nunits, (a).ntails, \
-      (a).rows, (a).k
-
-template <int K, bool PIPE>
-hipError_t launch_static(const RaggedLaunch& a, hipStream_t s) {
+template <int K, bool SET>
+hipError_t launch_vectors(const RaggedLaunch& a, hipStream_t s) {
   constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
-  // The static pipelined apply launch's block budget (rs_apply.hip, pipe_blocks).
-  const uint64_t blocks = ragged_blocks(K <= 12 ? 256 : 1024, a);
-  hipLaunchKernelGGL((ragged::rs_apply_ragged_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, false, PIPE>),
-                     dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_RAGGED_ARGS(a), nullptr);
-  return hipGetLastError();
-}
-
-template <int K>
-hipError_t dispatch(const RaggedLaunch& a, hipStream_t s) {
-  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
-  if (!pipelined_kernels()) return launch_static<K, false>(a, s);
-  // The dynamic schedule has nothing to balance over one block's units (queue_spread, kernels.hpp).
-  if (queue_allowed(s) && a.nunits > tiny_queue_units()) {
-    bool launched = false;
-    const uint64_t blocks = ragged_blocks(kQueueBlocks, a);
-    const hipError_t e = with_tickets(
-        s,
-        [&](uint32_t* set) {
-          hipLaunchKernelGGL((ragged::rs_apply_ragged_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, true, true>),
+  // The static forms take the static pipelined apply launch's block budget (rs_apply.hip, pipe_blocks).
+  return ragged::launch_scheduled(
+      s, a.w.nunits, a.w.ntails, K <= 12 ? 256 : 1024, [&](auto dyn, auto pipe, uint64_t blocks, uint32_t* set) {
+        constexpr bool DYN = decltype(dyn)::value, PIPE = decltype(pipe)::value;
+        if constexpr (SET)
+          hipLaunchKernelGGL((ragged::rs_apply_planned_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, DYN, PIPE>),
+                             dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_PLANNED_ARGS(a), set);
+        else
+          hipLaunchKernelGGL((ragged::rs_apply_ragged_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, DYN, PIPE>),
                              dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_RAGGED_ARGS(a), set);
-          return hipGetLastError();
-        },
-        &launched);
-    if (launched || e != hipSuccess) return e;
-  }
-  return launch_static<K, true>(a, s);
+        return hipGetLastError();
+      });
 }
 
 hipError_t launch_columns(const RaggedLaunch& a, hipStream_t s) {
-  const uint64_t blocks = ragged_blocks(1024, a);
-  hipLaunchKernelGGL(ragged::rs_apply_ragged_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
-                     SLIME_RAGGED_ARGS(a), 256u * (uint32_t)a.U, (uint32_t)a.C);
+  const uint64_t blocks = ragged::ragged_blocks(1024, a.w.nunits, a.w.ntails);
+  if (a.p.table)
+    hipLaunchKernelGGL(ragged::rs_apply_planned_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                       SLIME_PLANNED_ARGS(a), 256u * (uint32_t)a.w.U, (uint32_t)a.w.C);
+  else
+    hipLaunchKernelGGL(ragged::rs_apply_ragged_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                       SLIME_RAGGED_ARGS(a), 256u * (uint32_t)a.w.U, (uint32_t)a.w.C);
   return hipGetLastError();
 }
 
 #undef SLIME_RAGGED_ARGS
-
-// The planned launches: the same grids and the same choice between the
-// schedules as the single-plan launches above.
-#define SLIME_PLANNED_ARGS(a) (a).in, (a).out, (a).desc, (a).units, (a).tails, (a).table, (a).nunits, (a).ntails, (a).k
-
-template <int K, bool PIPE>
-hipError_t launch_planned_static(const PlannedLaunch& a, hipStream_t s) {
-  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
-  const uint64_t blocks = ragged_blocks(K <= 12 ? 256 : 1024, a);
-  hipLaunchKernelGGL((ragged::rs_apply_planned_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, false, PIPE>),
-                     dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_PLANNED_ARGS(a), nullptr);
-  return hipGetLastError();
-}
-
-template <int K>
-hipError_t dispatch_planned(const PlannedLaunch& a, hipStream_t s) {
-  constexpr int U = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K);
-  if (!pipelined_kernels()) return launch_planned_static<K, false>(a, s);
-  if (queue_allowed(s) && a.nunits > tiny_queue_units()) {
-    bool launched = false;
-    const uint64_t blocks = ragged_blocks(kQueueBlocks, a);
-    const hipError_t e = with_tickets(
-        s,
-        [&](uint32_t* set) {
-          hipLaunchKernelGGL((ragged::rs_apply_planned_kernel<K, U, C, kQueueCounters, kNtLoads, kNtStores, true, true>),
-                             dim3((uint32_t)blocks), dim3(kBlock), 0, s, SLIME_PLANNED_ARGS(a), set);
-          return hipGetLastError();
-        },
-        &launched);
-    if (launched || e != hipSuccess) return e;
-  }
-  return launch_planned_static<K, true>(a, s);
-}
-
-hipError_t launch_planned_columns(const PlannedLaunch& a, hipStream_t s) {
-  const uint64_t blocks = ragged_blocks(1024, a);
-  hipLaunchKernelGGL(ragged::rs_apply_planned_column_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
-                     SLIME_PLANNED_ARGS(a), 256u * (uint32_t)a.U, (uint32_t)a.C);
-  return hipGetLastError();
-}
-
 #undef SLIME_PLANNED_ARGS
 
 }  // namespace
 
 hipError_t launch_apply_ragged(const RaggedLaunch& a, hipStream_t s) {
   (void)hipGetLastError();  // report only this launch's error, not one left on the thread
-  if ((a.nunits == 0 && a.ntails == 0) || a.rows == 0) return hipSuccess;
-  if (a.k > 16 || !a.vec_ok) return launch_columns(a, s);
+  if (a.w.nunits == 0 && a.w.ntails == 0) return hipSuccess;
+  const bool set = a.p.table != nullptr;
+  if (!set && a.p.rows == 0) return hipSuccess;
+  if (a.w.k > 16 || !a.w.vec_ok) return launch_columns(a, s);
   // The vector kernels are instantiated with the geometry of their K: the tables must be cut by it.
-  if (a.U != ragged::unroll_for_k((int)a.k) || a.C != ragged::unit_tiles_for_k((int)a.k)) return hipErrorInvalidValue;
-  switch (a.k) {
-    case 1: return dispatch<1>(a, s);
-    case 2: return dispatch<2>(a, s);
-    case 3: return dispatch<3>(a, s);
-    case 4: return dispatch<4>(a, s);
-    case 5: return dispatch<5>(a, s);
-    case 6: return dispatch<6>(a, s);
-    case 7: return dispatch<7>(a, s);
-    case 8: return dispatch<8>(a, s);
-    case 9: return dispatch<9>(a, s);
-    case 10: return dispatch<10>(a, s);
-    case 11: return dispatch<11>(a, s);
-    case 12: return dispatch<12>(a, s);
-    case 13: return dispatch<13>(a, s);
-    case 14: return dispatch<14>(a, s);
-    case 15: return dispatch<15>(a, s);
-    default: return dispatch<16>(a, s);
-  }
-}
-
-hipError_t launch_apply_planned(const PlannedLaunch& a, hipStream_t s) {
-  (void)hipGetLastError();  // report only this launch's error, not one left on the thread
-  if (a.nunits == 0 && a.ntails == 0) return hipSuccess;
-  if (a.k > 16 || !a.vec_ok) return launch_planned_columns(a, s);
-  if (a.U != ragged::unroll_for_k((int)a.k) || a.C != ragged::unit_tiles_for_k((int)a.k)) return hipErrorInvalidValue;
-  switch (a.k) {
-    case 1: return dispatch_planned<1>(a, s);
-    case 2: return dispatch_planned<2>(a, s);
-    case 3: return dispatch_planned<3>(a, s);
-    case 4: return dispatch_planned<4>(a, s);
-    case 5: return dispatch_planned<5>(a, s);
-    case 6: return dispatch_planned<6>(a, s);
-    case 7: return dispatch_planned<7>(a, s);
-    case 8: return dispatch_planned<8>(a, s);
-    case 9: return dispatch_planned<9>(a, s);
-    case 10: return dispatch_planned<10>(a, s);
-    case 11: return dispatch_planned<11>(a, s);
-    case 12: return dispatch_planned<12>(a, s);
-    case 13: return dispatch_planned<13>(a, s);
-    case 14: return dispatch_planned<14>(a, s);
-    case 15: return dispatch_planned<15>(a, s);
-    default: return dispatch_planned<16>(a, s);
-  }
+  if (a.w.U != ragged::unroll_for_k((int)a.w.k) || a.w.C != ragged::unit_tiles_for_k((int)a.w.k))
+    return hipErrorInvalidValue;
+  return ragged::with_k(a.w.k, [&](auto kc) {
+    constexpr int K = decltype(kc)::value;
+    return set ? launch_vectors<K, true>(a, s) : launch_vectors<K, false>(a, s);
+  });
 }
 
 }  // namespace slime

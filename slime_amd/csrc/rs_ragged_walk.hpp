@@ -171,6 +171,29 @@ __device__ __forceinline__ PlanRef load_plan(const uint32_t* __restrict__ tab, c
   const apply::u32x4 v = *reinterpret_cast<const apply::u32x4*>(tab + (uint64_t)plan * planset::kRecordWords);
   return PlanRef{v[0], v[1], v[2], v[3]};
 }
+// The same record read by ONE LANE through its item's descriptor (the tail
+// items: neighbouring lanes hold different objects).
+__device__ __forceinline__ PlanRef read_plan(const uint32_t* __restrict__ tab, const Desc* d) {
+  const uint32_t* const rec = tab + (uint64_t)d->reserved[0] * planset::kRecordWords;
+  return PlanRef{rec[0], rec[1], rec[2], rec[3]};
+}
+
+// A plan's rows as a launch reads them (verify: one row block of the plan).
+struct PlanRows {
+  const uint32_t* coeff;
+  const uint32_t* oidx;
+  uint32_t rows;
+};
+// The rows of a plan that fall into a verify launch's row block [r0, r0 + 64).
+__device__ __forceinline__ uint32_t block_rows(uint32_t rows, uint32_t r0) {
+  return rows > r0 ? (rows - r0 < 64u ? rows - r0 : 64u) : 0u;
+}
+// The plan with record p of the set's table `tab`, whole (byte decode); its
+// input indices are at tab + p.in_off.  Verify reads one row block of it
+// (rs_verify_ragged_kernel.hpp).
+__device__ __forceinline__ PlanRows whole_plan(const uint32_t* tab, const PlanRef& p) {
+  return PlanRows{tab + p.coeff_off, tab + p.out_off, p.rows};
+}
 
 }  // namespace ragged
 }  // namespace slime

@@ -41,6 +41,7 @@
 
 #include "kernels.hpp"
 #include "rs_apply_kernel.hpp"
+#include "rs_ragged_launch.hpp"  // with_k
 #include "rs_verify_kernel.hpp"  // Tally, load_tile, check_tile, check_columns: shared with rs_verify_ragged.hip
 
 namespace slime {
@@ -257,26 +258,8 @@ hipError_t launch_columns(const VerifyLaunch& v, uint32_t r0, uint32_t rows_c, h
 }
 
 hipError_t launch_block(const VerifyLaunch& v, uint32_t r0, uint32_t rows_c, hipStream_t s) {
-  if (!v.vec_ok) return launch_columns(v, r0, rows_c, s);
-  switch (v.k) {
-    case 1: return launch_rows<1>(v, r0, rows_c, s);
-    case 2: return launch_rows<2>(v, r0, rows_c, s);
-    case 3: return launch_rows<3>(v, r0, rows_c, s);
-    case 4: return launch_rows<4>(v, r0, rows_c, s);
-    case 5: return launch_rows<5>(v, r0, rows_c, s);
-    case 6: return launch_rows<6>(v, r0, rows_c, s);
-    case 7: return launch_rows<7>(v, r0, rows_c, s);
-    case 8: return launch_rows<8>(v, r0, rows_c, s);
-    case 9: return launch_rows<9>(v, r0, rows_c, s);
-    case 10: return launch_rows<10>(v, r0, rows_c, s);
-    case 11: return launch_rows<11>(v, r0, rows_c, s);
-    case 12: return launch_rows<12>(v, r0, rows_c, s);
-    case 13: return launch_rows<13>(v, r0, rows_c, s);
-    case 14: return launch_rows<14>(v, r0, rows_c, s);
-    case 15: return launch_rows<15>(v, r0, rows_c, s);
-    case 16: return launch_rows<16>(v, r0, rows_c, s);
-    default: return launch_columns(v, r0, rows_c, s);
-  }
+  if (!v.vec_ok || v.k < 1 || v.k > 16) return launch_columns(v, r0, rows_c, s);
+  return ragged::with_k(v.k, [&](auto kc) { return launch_rows<decltype(kc)::value>(v, r0, rows_c, s); });
 }
 
 #undef SLIME_VERIFY_ARGS
