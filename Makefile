@@ -8,7 +8,7 @@ SRC      := slime_amd/csrc
 OBJ      := build/obj
 LIB      := slime_amd/lib/libslime_rs.so
 
-OBJS := $(OBJ)/rs_apply.o $(OBJ)/rs_apply_k32.o $(OBJ)/rs_apply_mfma.o $(OBJ)/rs_verify.o $(OBJ)/rs_ragged.o $(OBJ)/rs_verify_ragged.o $(OBJ)/rs_bytes.o $(OBJ)/rs_bytes_k32.o $(OBJ)/rs_bytes_mfma.o $(OBJ)/rs_bytes_ragged.o $(OBJ)/rs_bytes_ragged_encode.o $(OBJ)/gf_codec.o $(OBJ)/host_blit.o $(OBJ)/rs_matrix.o $(OBJ)/host_copy.o $(OBJ)/host_codec.o $(OBJ)/digest.o $(OBJ)/device_alloc.o $(OBJ)/host_pipeline.o $(OBJ)/go_api.o $(OBJ)/object_calls.o $(OBJ)/rs_capi.o
+OBJS := $(OBJ)/rs_apply.o $(OBJ)/rs_apply_k32.o $(OBJ)/rs_apply_mfma.o $(OBJ)/rs_verify.o $(OBJ)/rs_ragged.o $(OBJ)/rs_verify_ragged.o $(OBJ)/rs_locate_ragged.o $(OBJ)/rs_bytes.o $(OBJ)/rs_bytes_k32.o $(OBJ)/rs_bytes_mfma.o $(OBJ)/rs_bytes_ragged.o $(OBJ)/rs_bytes_ragged_encode.o $(OBJ)/gf_codec.o $(OBJ)/host_blit.o $(OBJ)/rs_matrix.o $(OBJ)/host_copy.o $(OBJ)/host_codec.o $(OBJ)/digest.o $(OBJ)/device_alloc.o $(OBJ)/host_pipeline.o $(OBJ)/go_api.o $(OBJ)/object_calls.o $(OBJ)/rs_capi.o
 HDRS := $(wildcard $(SRC)/*.hpp) include/slime_rs.h
 
 CXXTEST  := tests/cpp/rs_host_test
@@ -24,9 +24,10 @@ PLANSETTEST := tests/cpp/planset_table_test
 STEPTEST := tests/cpp/verify_step_test
 PROBETEST := tests/cpp/probe_layout_test
 EDGETEST := tests/cpp/encode_edge_test
+LOCATETEST := tests/cpp/locate_rule_test
 PROXYLOAD := tools/libproxy_load.so
 
-all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(PROXYLOAD)
+all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(LOCATETEST) $(PROXYLOAD)
 
 # Proxy-level load generator over the C-ABI (bench.py host_path.pooled): C++ threads, no GIL.
 $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(LIB)
@@ -45,6 +46,10 @@ $(EDGETEST): tests/cpp/encode_edge_test.cpp $(SRC)/encode_edge.hpp
 #   make tests/cpp/encode_edge_test_asan && tests/cpp/encode_edge_test_asan
 $(EDGETEST)_asan: tests/cpp/encode_edge_test.cpp $(SRC)/encode_edge.hpp
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Wall -Wextra -I$(SRC) -o $@ tests/cpp/encode_edge_test.cpp
+
+# The locate rule (locate_rule.hpp) over the product's parity matrices against a brute-force restatement, CPU only.
+$(LOCATETEST): tests/cpp/locate_rule_test.cpp $(SRC)/locate_rule.hpp $(SRC)/gfp.hpp $(SRC)/gfp_host.hpp $(SRC)/rs_matrix.cpp $(SRC)/rs_matrix.hpp
+	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/locate_rule_test.cpp $(SRC)/rs_matrix.cpp
 
 # The ragged batch's host work tables (ragged_plan.hpp), CPU only.
 $(RAGGEDTEST): tests/cpp/ragged_plan_test.cpp $(SRC)/ragged_plan.hpp
@@ -108,7 +113,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(EDGETEST)_asan
+	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(EDGETEST)_asan $(LOCATETEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -393,9 +393,10 @@ int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batc
  * anything else one column a lane (correct, not fast).  The ragged and planned
  * forms of slime_rs_verify_objects are slime_rs_verify_objects_batch and
  * slime_rs_planset_verify_objects_batch below, and what they scrub is written
- * by the ragged byte encode (slime_rs_encode_objects_batch).  Out of scope:
- * matrix-core forms (matrix-core or k-template ragged verify for wide codes),
- * locating which shard is wrong. */
+ * by the ragged byte encode (slime_rs_encode_objects_batch).  Verify tells
+ * which rows disagree; which SHARD is wrong is slime_rs_plan_locate_batch
+ * below, which takes these mismatch counts as its filter.  Out of scope:
+ * matrix-core forms (matrix-core or k-template ragged verify for wide codes). */
 int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
                                const uint32_t *cmp, uint64_t *mismatches, uint64_t *first, void *stream);
 int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src,
@@ -459,6 +460,63 @@ int slime_rs_verify_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, 
 int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
                                           const uint8_t *cmp, const uint32_t *mapping, uint64_t *mismatches,
                                           uint64_t *first, void *stream);
+
+/* ---- ragged locate: name the corrupt shards of scrubbed objects ----------------
+ * The step between scrub and repair.  Verify reports which parity ROWS of an
+ * object disagree; a repair (slime_rs_planset_execute_batch) needs to know
+ * which SHARD to rebuild.  With rows >= 2 the code answers that itself: one
+ * wrong shard in a column is identified by that column's syndrome.
+ * The rule, per column b of object o, for a plan with k inputs and rows output
+ * rows c[i][j]: computed_i is the canonical residue of row i over the stored
+ * inputs, d_i is set iff the stored word of row i is not bit-identical to
+ * computed_i (verify's rule: a stored p+3 where 3 is computed counts), and
+ * s_i = (stored_i mod p - computed_i) mod p.  The column is
+ *   clean         no d_i set;
+ *   output row i  exactly one d_i set: slot k + i;
+ *   input j       J = { j : s_0 != 0 and s_i*c[0][j] == s_0*c[i][j] (mod p) for
+ *                 all i } has exactly one member: slot j;
+ *   unlocated     anything else: slot k + rows.
+ * For the plans this library builds (encode and reconstruct plans of the MDS
+ * code) a single wrong shard in a column is always named.  TWO OR MORE wrong
+ * shards in ONE column are beyond what `rows` syndromes can decide: such a
+ * column is reported as unlocated, or, with probability about k/p per such
+ * column, blamed on a third shard.  Wrong shards in DIFFERENT columns of one
+ * object are each named.  For slime_rs_plan_matrix plans the rule is applied as
+ * written, whatever the matrix.
+ * Addressing is exactly slime_rs_plan_verify_batch's (and, for the byte form,
+ * slime_rs_verify_objects_batch's: symbol = BE(word) ^ mapping[o]): inputs
+ * through the span's src side, stored rows through its dst side at the plan's
+ * output shards; cmp may be src.  A planned batch is accepted; objects with
+ * SLIME_RS_NO_PLAN or L == 0 are skipped.
+ * Results: two device arrays of nobj x (k + rows + 1) uint64, row-major:
+ * counts[o][slot] is the number of columns blamed on slot, first[o][slot] the
+ * lowest such column inside the object or UINT64_MAX.  Slots 0..k-1 are the
+ * plan's inputs in its own order, k..k+rows-1 its output rows, k+rows is
+ * `unlocated`.  The call initialises both arrays on the stream whenever
+ * nobj > 0 (one kernel node, as verify: replays of a captured graph start
+ * clean), writes nothing else and uses no scratch.
+ * filter: NULL, or the `mismatches` array of a preceding verify of the same
+ * plan and batch on the same stream (nobj x rows).  An object whose `rows`
+ * entries are all zero is passed over without reading its data and keeps the
+ * initial values; NULL scans every object.  The filter is read on the device:
+ * verify followed by locate is one capturable chain with no host round trip.
+ * Asynchronous, and capturable under the rules of slime_rs_plan_verify_batch
+ * (the walk is static in every schedule mode: no counter set is taken).  Marks
+ * the plan as launched.  SLIME_RS_ERR_INVALID_ARG: null arguments (filter may
+ * be NULL), a plan whose k or device is not the batch's, rows < 2 (one parity
+ * row cannot tell which shard is wrong), k + rows > 63 (a wave's running tally
+ * keeps one slot per lane).
+ * Forms: k <= 16 over 4-byte aligned src and cmp runs four columns a lane,
+ * anything else one column a lane (correct, not fast).  Out of scope:
+ * uniform-layout entry points (a uniform batch is a packed batch of equal
+ * lengths), plan-set locate, matrix-core forms and k + rows > 63, correcting
+ * more than one wrong shard per column, device digests. */
+int slime_rs_plan_locate_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
+                               const uint32_t *cmp, const uint64_t *filter, uint64_t *counts, uint64_t *first,
+                               void *stream);
+int slime_rs_locate_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t *src,
+                                  const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
+                                  uint64_t *counts, uint64_t *first, void *stream);
 
 /* ---- ragged byte encode: ingest objects of different sizes in one launch -------
  * slime_rs_encode_objects over the spans of a batch, each object with its own

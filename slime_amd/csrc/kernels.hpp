@@ -393,6 +393,30 @@ struct RaggedBytesVerifyLaunch {
 };
 hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStream_t stream);
 
+// --- ragged locate (rs_locate_ragged.hip) ------------------------------------------
+// launch_verify_ragged's addressing, one plan; the answer is per SHARD instead
+// of per row: every column b < L_o of every object is classified by the rule
+// of locate_rule.hpp, counts[o*(k+rows+1) + slot] = the columns blamed on slot
+// (0..k-1: the plan's inputs, k..k+rows-1: its rows, k+rows: unlocated) and
+// first[...] = the lowest of them or UINT64_MAX.  mapping != nullptr: stored
+// chunk bytes, symbol = BE(word) ^ mapping[o].  filter: nullptr, or the nobj x
+// rows mismatch counts of a preceding verify on the stream -- an object whose
+// entries are all zero is passed over on the device without reading its data.
+// Needs 2 <= rows and k + rows <= 63.  The launch initialises both result
+// arrays with rs_verify_init_kernel whenever w.nobj > 0, writes nothing else
+// and uses no scratch; a static walk in every schedule mode.
+struct RaggedLocateLaunch {
+  const void* in;
+  const void* cmp;
+  RaggedWork w;
+  RaggedPlan p;             // one plan
+  const uint32_t* mapping;  // bytes: nobj mapping values (device); symbols: nullptr
+  const uint64_t* filter;
+  uint64_t* counts;
+  uint64_t* first;
+};
+hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t stream);
+
 // --- ragged byte encode (rs_bytes_ragged_encode.hip) ------------------------------
 // The fused byte encode over a ragged batch: object o of sizes[o] bytes, its k
 // data chunks read (and their tails rewritten) through the descriptor's src

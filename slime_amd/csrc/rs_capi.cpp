@@ -867,6 +867,50 @@ int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch
   return 0;
 }
 
+// ---- ragged locate (rs_locate_ragged.hip) -------------------------------------------
+
+// What both locate forms check after check_batch_plan, symbols or bytes, in this order.
+static int check_locate_batch(const char* what, const slime_rs_plan* plan, const void* src, const void* cmp,
+                              const uint64_t* counts, const uint64_t* first) {
+  if (plan->rows < 2)
+    return fail(Status::InvalidArg, std::string(what) + ": the plan has " + std::to_string(plan->rows) +
+                                        " row: one parity row cannot tell which shard is wrong");
+  if (plan->k + plan->rows > 63)
+    return fail(Status::InvalidArg, std::string(what) + ": k + rows = " + std::to_string(plan->k + plan->rows) +
+                                        " exceeds 63 (a wave's tally keeps one slot per lane)");
+  if (!counts || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  return 0;
+}
+
+int slime_rs_plan_locate_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, const uint32_t* cmp,
+                               const uint64_t* filter, uint64_t* counts, uint64_t* first, void* stream) {
+  if (int rc = check_batch_plan("plan_locate_batch", plan, batch)) return rc;
+  if (int rc = check_locate_batch("plan_locate_batch", plan, src, cmp, counts, first)) return rc;
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  const RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), nullptr, filter, counts, first};
+  // A locate reads the plan's output table like any launch (slime_rs_plan_set_outputs).
+  plan->executed.store(true, std::memory_order_relaxed);
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+int slime_rs_locate_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src, const uint8_t* cmp,
+                                  const uint32_t* mapping, const uint64_t* filter, uint64_t* counts, uint64_t* first,
+                                  void* stream) {
+  if (int rc = check_batch_plan("locate_objects_batch", plan, batch)) return rc;
+  if (int rc = check_locate_batch("locate_objects_batch", plan, src, cmp, counts, first)) return rc;
+  // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
+  if (!mapping) return fail(Status::InvalidArg, "locate_objects_batch: null mapping");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  const RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), mapping, filter, counts, first};
+  plan->executed.store(true, std::memory_order_relaxed);
+  DeviceScope ds(plan->device);
+  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
   if (!plan || !out_shards) return fail(Status::InvalidArg, "plan_set_outputs: bad args");
   // The table rewrite below is a synchronous copy that nothing orders against

@@ -1,0 +1,119 @@
+// Ragged locate for CDNA4 (gfx950): after a scrub (rs_verify_ragged.hip) said
+// WHICH ROWS of an object disagree, this launch says WHICH SHARD is wrong, per
+// column, by the rule of locate_rule.hpp -- slime_rs_plan_locate_batch over
+// symbols, slime_rs_locate_objects_batch over stored chunk bytes.  Results:
+// counts[o][slot] columns blamed on slot, first[o][slot] the lowest of them;
+// slots are the plan's k inputs, its rows, then `unlocated`.
+//
+// Fast path -- verify's: the work comes from UnitWalk over the batch's unit
+// list (rs_ragged_walk.hpp), a tile goes in verify's steps (verify_step.hpp),
+// load_tile loads a step and dot4 computes its rows.  Instead of a tally per
+// row, every row's word deltas are OR-ed into a per-lane mask across all row
+// blocks (flag_tile): clean data costs verify's loads and math plus that OR,
+// with no atomics and no stores.  A unit whose object the filter clears (all
+// of a preceding verify's counts zero, read here on the device) is passed over
+// before any load.
+//
+// Rare path -- only when a ballot of the mask is non-zero: a lane with a
+// flagged column re-reads that column's k inputs and `rows` stored words (just
+// loaded: cache hits) and classifies it (classify_column), keeping s_0, the
+// count of mismatching rows, the last such row and a 64-bit mask of the inputs
+// that still satisfy the relation -- no per-row arrays, nothing in scratch.
+//
+// Tallying: a wave's classified columns are folded slot by slot (ballot /
+// readlane over the distinct slots present) into verify's Tally with lane =
+// slot -- hence k + rows <= 63 -- and flushed with atomicAdd / atomicMin when
+// the wave moves to another object and at the end of the walk.  Tail items
+// (L % 4 columns an object) classify one column a lane and issue their own
+// atomics.
+//
+// Forms:
+//   k <= 16, 4-byte aligned src and cmp: rs_locate_ragged_kernel<K, W, R, ...>,
+//     four columns a lane, symbols and bytes from one body (BYTES).
+//   17 <= k (k + rows <= 63), or a base that is not 4-byte aligned:
+//     rs_locate_ragged_column_kernel, one column a lane over the same unit list.
+// Walk: static, one step at a time, in every schedule / pipeline mode (so the
+// modes cannot differ); latency is hidden by occupancy, four blocks a CU.
+// Only plain C++ and vector atomics write memory.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+#include "rs_locate_ragged_kernel.hpp"
+#include "rs_ragged_launch.hpp"
+#include "verify_step.hpp"
+
+namespace slime {
+namespace locate {
+
+template <int K, int W, int R, int UB, int C, bool BYTES>
+__global__ __launch_bounds__(kBlock) void rs_locate_ragged_kernel(SLIME_RLOCATE_PARAMS) {
+  locate_ragged_vectors<K, W, R, UB, C, BYTES>(SLIME_RLOCATE_PASS);
+}
+
+template <bool BYTES>
+__global__ __launch_bounds__(kBlock) void rs_locate_ragged_column_kernel(SLIME_RLOCATE_PARAMS, uint32_t tile_cols,
+                                                                         uint32_t unit_tiles) {
+  locate_ragged_columns<BYTES>(SLIME_RLOCATE_PASS, tile_cols, unit_tiles);
+}
+
+}  // namespace locate
+
+namespace {
+
+using apply::kBlock;
+
+#define SLIME_RLOCATE_ARGS(v)                                                                                     \
+  (const uint8_t*)(v).in, (const uint8_t*)(v).cmp, (v).w.desc, (v).w.units, (v).w.tails, (v).p.coeff,             \
+      (v).p.in_idx, (v).p.out_idx, (v).mapping, (const unsigned long long*)(v).filter,                            \
+      (unsigned long long*)(v).counts, (unsigned long long*)(v).first, (v).w.nunits, (v).w.ntails, (v).p.rows,    \
+      (v).w.k
+
+constexpr uint64_t kLocateBlocks = 1024;  // four blocks a CU: the static walk hides latency by occupancy
+
+template <int K, int R, bool BYTES>
+hipError_t launch_vectors(const RaggedLocateLaunch& v, hipStream_t s) {
+  constexpr int UB = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K), W = verify_step::width(K, R);
+  const uint64_t blocks = ragged::ragged_blocks(kLocateBlocks, v.w.nunits, v.w.ntails);
+  hipLaunchKernelGGL((locate::rs_locate_ragged_kernel<K, W, R, UB, C, BYTES>), dim3((uint32_t)blocks), dim3(kBlock), 0,
+                     s, SLIME_RLOCATE_ARGS(v));
+  return hipGetLastError();
+}
+
+template <int K>
+hipError_t launch_rows(const RaggedLocateLaunch& v, hipStream_t s) {
+  const bool bytes = v.mapping != nullptr;
+  if (verify_step::stored_rows(v.p.rows) == 2)
+    return bytes ? launch_vectors<K, 2, true>(v, s) : launch_vectors<K, 2, false>(v, s);
+  return bytes ? launch_vectors<K, 4, true>(v, s) : launch_vectors<K, 4, false>(v, s);
+}
+
+hipError_t launch_columns(const RaggedLocateLaunch& v, hipStream_t s) {
+  const uint64_t blocks = ragged::ragged_blocks(kLocateBlocks, v.w.nunits, v.w.ntails);
+  if (v.mapping)
+    hipLaunchKernelGGL(locate::rs_locate_ragged_column_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                       SLIME_RLOCATE_ARGS(v), 256u * (uint32_t)v.w.U, (uint32_t)v.w.C);
+  else
+    hipLaunchKernelGGL(locate::rs_locate_ragged_column_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                       SLIME_RLOCATE_ARGS(v), 256u * (uint32_t)v.w.U, (uint32_t)v.w.C);
+  return hipGetLastError();
+}
+
+#undef SLIME_RLOCATE_ARGS
+
+}  // namespace
+
+hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t s) {
+  (void)hipGetLastError();  // report only this launch's error, not one left on the thread
+  if (v.w.nobj == 0) return hipSuccess;
+  if (v.p.rows < 2 || v.w.k + v.p.rows > locate::kMaxSlots) return hipErrorInvalidValue;
+  if (hipError_t e = launch_verify_init(v.counts, v.first, v.w.nobj * (v.w.k + v.p.rows + 1), s)) return e;
+  if (v.w.nunits == 0 && v.w.ntails == 0) return hipSuccess;  // an empty batch: nothing but the initialisation
+  const bool vec = v.w.k <= 16 && v.w.vec_ok;
+  // The vector kernels are instantiated with the geometry of their K: the tables must be cut by it.
+  if (vec && (v.w.U != ragged::unroll_for_k((int)v.w.k) || v.w.C != ragged::unit_tiles_for_k((int)v.w.k)))
+    return hipErrorInvalidValue;
+  if (!vec) return launch_columns(v, s);
+  return ragged::with_k(v.w.k, [&](auto kc) { return launch_rows<decltype(kc)::value>(v, s); });
+}
+
+}  // namespace slime

@@ -1,0 +1,289 @@
+// Device side of the ragged locate (rs_locate_ragged.hip), symbols and stored
+// chunk bytes alike (BYTES: a stored word is big-endian and XOR-ed with its
+// object's mapping value, so every symbol is BE(word) ^ m): the filter's
+// verdict on an object, the fast path's per-lane mismatch flags, the rare
+// path's classification of one column by locate_rule.hpp, the fold of a wave's
+// classified columns into a Tally (lane = slot), the tail items and the
+// one-column-a-lane form.  rs_locate_ragged.hip's header comment describes the
+// scheme.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "locate_rule.hpp"
+#include "rs_apply_kernel.hpp"
+#include "rs_ragged_walk.hpp"
+#include "rs_verify_kernel.hpp"
+
+namespace slime {
+namespace locate {
+
+using apply::kBlock;
+using apply::kWaves;
+using ragged::Desc;
+using ragged::ObjRef;
+using ragged::Tail;
+using ragged::Unit;
+using ragged::UnitWalk;
+using verify::be;
+using verify::Tally;
+
+// coeff / in_idx / out_idx / rows / k: the plan's; mapping: BYTES only; filter: NULL or nobj x rows
+// counts of a preceding verify; counts / first: nobj x (k + rows + 1).
+#define SLIME_RLOCATE_PARAMS                                                                                      \
+  const uint8_t *__restrict__ in, const uint8_t *__restrict__ cmp, const Desc *__restrict__ descs,                \
+      const Unit *__restrict__ units, const Tail *__restrict__ tails, const uint32_t *__restrict__ coeff,         \
+      const uint32_t *__restrict__ in_idx, const uint32_t *__restrict__ out_idx,                                  \
+      const uint32_t *__restrict__ mapping, const unsigned long long *__restrict__ filter,                        \
+      unsigned long long *__restrict__ counts, unsigned long long *__restrict__ first, uint32_t nunits,           \
+      uint64_t ntails, uint32_t rows, uint32_t k
+#define SLIME_RLOCATE_PASS \
+  in, cmp, descs, units, tails, coeff, in_idx, out_idx, mapping, filter, counts, first, nunits, ntails, rows, k
+
+// true: the filter clears object obj -- all `rows` counts of the verify are zero -- and the launch
+// passes over it before any load of its data.
+__device__ __forceinline__ bool filtered_out(const unsigned long long* __restrict__ filter, uint32_t obj,
+                                             uint32_t rows) {
+  if (!filter) return false;
+  unsigned long long any = 0;
+  for (uint32_t i = 0; i < rows; ++i) any |= filter[(uint64_t)obj * rows + i];
+  return any == 0;
+}
+
+// The slot of column `col` of the object at ib / cb (bytes; shard strides in bytes), by the rule.
+// Re-reads the column's k inputs for every row and its `rows` stored words: the rare path, on
+// words the fast path has just loaded.  No per-row arrays.
+template <bool BYTES>
+__device__ __forceinline__ uint32_t classify_column(const uint8_t* ib, const uint8_t* cb,
+                                                    const uint32_t* __restrict__ coeff,
+                                                    const uint32_t* __restrict__ in_idx, uint64_t in_shard,
+                                                    const uint32_t* __restrict__ out_idx, uint64_t cmp_shard,
+                                                    uint32_t rows, uint32_t k, uint32_t m, uint64_t col) {
+  const uint32_t cs = apply::wide_coeff_stride(k);
+  auto in_word = [&](uint32_t j) {
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(ib + (uint64_t)in_idx[j] * in_shard + (col << 2));
+    return BYTES ? be(v) ^ m : v;
+  };
+  Column c;
+  c.begin(k);
+  for (uint32_t i = 0; i < rows; ++i) {
+    const uint32_t* const ci = coeff + (uint64_t)i * cs;
+    const uint32_t computed = apply::wide_dot(ci, k, in_word);
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(cb + (uint64_t)out_idx[i] * cmp_shard + (col << 2));
+    c.row(i, computed, BYTES ? be(w) ^ m : w, coeff, ci);
+  }
+  return c.slot(k, rows);
+}
+
+// Folds a wave's classified columns into its Tally, slot by slot: `slot` is this lane's column's
+// slot or kNoSlot, `col` its column; the lanes hold columns in ascending order, so the lowest lane
+// of a slot holds its lowest column.
+__device__ __forceinline__ void tally_slots(Tally& t, uint32_t slot, uint64_t col) {
+  uint64_t left = __ballot(slot != kNoSlot);
+  while (left) {
+    const int l = __ffsll((unsigned long long)left) - 1;
+    const uint32_t sl = (uint32_t)__builtin_amdgcn_readlane((int)slot, l);
+    const uint64_t same = __ballot(slot == sl);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)col, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(col >> 32), l);
+    t.add(sl, (uint32_t)__popcll(same), ((uint64_t)hi << 32) | lo);
+    left &= ~same;
+  }
+}
+
+// Fast path of one step: vectors [tb, tb + 64 U) clipped to v1, inputs x and the first R stored
+// rows s already loaded.  Every row's word deltas are OR-ed per lane across all row blocks;
+// returns bit 4u + w set iff word w of unit u has some mismatching row.  No atomics, no stores.
+template <int K, int U, int R, bool BYTES, class T>
+__device__ __forceinline__ uint32_t flag_tile(uint4 (&x)[U][K], uint4 (&s)[R][U], const uint8_t* cb,
+                                              const uint32_t* __restrict__ coeff,
+                                              const uint32_t* __restrict__ out_idx, uint64_t cmp_shard,
+                                              uint32_t rows, uint32_t m, T tb, T v1, uint32_t lane) {
+  if constexpr (BYTES) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        x[u][j] = make_uint4(be(x[u][j].x) ^ m, be(x[u][j].y) ^ m, be(x[u][j].z) ^ m, be(x[u][j].w) ^ m);
+  }
+  uint4 acc[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc[u] = make_uint4(0, 0, 0, 0);
+  auto block = [&](uint32_t r0) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      if (i == 0 || r0 + i < rows) {
+        const apply::CoeffRow<K> c = apply::load_coeff_row<K>(coeff, r0 + i);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const uint4 e = verify::delta4<BYTES>(apply::dot4<K>(x[u], c), s[i][u], m);
+          acc[u] = make_uint4(acc[u].x | e.x, acc[u].y | e.y, acc[u].z | e.z, acc[u].w | e.w);
+        }
+      }
+    }
+  };
+  block(0);
+  // Plans of more than R rows: the further row blocks, loaded here.
+  for (uint32_t r0 = R; r0 < rows; r0 += R) {
+    const uint8_t* rb[R];
+    verify::row_bases<R>(rb, cb, out_idx, cmp_shard, r0, rows);
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const T g = tb + 64 * u + lane < v1 ? tb + 64 * u + lane : v1 - 1;
+        s[i][u] = verify::ldv<T>(rb[i], g);
+      }
+    block(r0);
+  }
+  uint32_t bits = 0;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t d = (acc[u].x ? 1u : 0u) | (acc[u].y ? 2u : 0u) | (acc[u].z ? 4u : 0u) | (acc[u].w ? 8u : 0u);
+    if (tb + 64 * u + lane < v1) bits |= d << (4 * u);
+  }
+  return bits;
+}
+
+// The tail items: one {object, column} per lane, classified and counted by the lane itself
+// (neighbouring lanes hold different objects: Tally's lane-per-slot scheme does not apply).
+template <bool BYTES>
+__device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS) {
+  const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint64_t nthr = (uint64_t)gridDim.x * kBlock;
+  const uint32_t nslots = k + rows + 1;
+  for (uint64_t t = tid; t < ntails; t += nthr) {
+    const Tail it = tails[t];
+    if (filtered_out(filter, it.obj, rows)) continue;
+    const Desc* const d = descs + it.obj;
+    uint32_t m = 0;
+    if constexpr (BYTES) m = mapping[it.obj];
+    const uint32_t slot = classify_column<BYTES>(in + (d->src_off << 2), cmp + (d->dst_off << 2), coeff, in_idx,
+                                                 d->src_shard << 2, out_idx, d->dst_shard << 2, rows, k, m, it.col);
+    if (slot != kNoSlot) {
+      atomicAdd(counts + (uint64_t)it.obj * nslots + slot, 1ull);
+      atomicMin(first + (uint64_t)it.obj * nslots + slot, (unsigned long long)it.col);
+    }
+  }
+}
+
+// Four columns a lane, k = K <= 16 over 4-byte aligned bases: a static walk over the unit list,
+// a tile in verify's steps of W vectors a lane, one step at a time.
+template <int K, int W, int R, int UB, int C, bool BYTES>
+__device__ __forceinline__ void locate_ragged_vectors(SLIME_RLOCATE_PARAMS) {
+  static_assert(K > 0 && K <= 16 && W >= 1 && W <= UB && W <= 4, "compile-time k; a step is at most a tile");
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t nslots = k + rows + 1;
+  UnitWalk<C, 1, false> w(nullptr, units, descs, nunits, lane, wave, gridDim.x * kWaves);
+  Tally t(lane);
+  const uint8_t* sb[K];
+  const uint8_t* rb[R];
+#pragma unroll
+  for (int j = 0; j < K; ++j) sb[j] = in;
+#pragma unroll
+  for (int i = 0; i < R; ++i) rb[i] = cmp;
+  const uint8_t* ib = in;
+  const uint8_t* cb = cmp;
+  uint64_t ishard = 0, cshard = 0;
+  uint32_t m = 0;
+  bool skip = false;
+  while (w.live) {
+    if (w.fresh) {  // the first tile since the object changed
+      skip = filtered_out(filter, w.obj, rows);
+      if (!skip) {
+        if constexpr (BYTES) m = mapping[w.obj];  // wave-uniform
+        ib = in + (w.d.src_off << 2);
+        ishard = w.d.src_shard << 2;
+#pragma unroll
+        for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)in_idx[j] * ishard;
+        cb = cmp + (w.d.dst_off << 2);
+        cshard = w.d.dst_shard << 2;
+        verify::row_bases<R>(rb, cb, out_idx, cshard, 0, rows);
+        unsigned long long* const res = counts + (uint64_t)w.obj * nslots;
+        if (res != t.mism) {
+          t.flush();
+          t.begin(res, first + (uint64_t)w.obj * nslots);
+        }
+      }
+    }
+    if (!skip) {
+      const uint32_t t0 = w.tile() * (64 * UB);
+      const uint32_t tend = w.d.nvec - t0 < 64u * UB ? w.d.nvec : t0 + 64 * UB;  // the host lists tiles below nvec
+      for (uint32_t tb = t0; tb < tend; tb += 64 * W) {
+        uint4 x[W][K], s[R][W];
+        verify::load_tile<K, W, R, uint32_t>(x, s, sb, rb, tb + lane, tend);
+        const uint32_t bits = flag_tile<K, W, R, BYTES, uint32_t>(x, s, cb, coeff, out_idx, cshard, rows, m, tb, tend, lane);
+        if (__ballot(bits != 0)) {
+          // Rare path: word q & 3 of unit q >> 2, every lane that flagged it; for one q the lanes
+          // are in column order.
+          for (uint32_t q = 0; q < 4u * W; ++q) {
+            const bool hit = (bits >> q) & 1u;
+            if (!__ballot(hit)) continue;
+            const uint64_t col = ((uint64_t)(tb + 64 * (q >> 2) + lane) << 2) + (q & 3u);
+            uint32_t slot = kNoSlot;
+            if (hit) slot = classify_column<BYTES>(ib, cb, coeff, in_idx, ishard, out_idx, cshard, rows, k, m, col);
+            tally_slots(t, slot, col);
+          }
+        }
+      }
+    }
+    w.advance();
+  }
+  t.flush();
+  locate_tails<BYTES>(SLIME_RLOCATE_PASS);
+}
+
+// One column a lane over the same unit list (static walk): generic k through wide_dot, any
+// alignment.  tile_cols = 256 UB, unit_tiles = C of the batch's geometry.
+template <bool BYTES>
+__device__ __forceinline__ void locate_ragged_columns(SLIME_RLOCATE_PARAMS, uint32_t tile_cols, uint32_t unit_tiles) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t nwaves = gridDim.x * kWaves;
+  const uint32_t nslots = k + rows + 1, cs = apply::wide_coeff_stride(k);
+  Tally t(lane);
+  for (uint64_t e = wave; e < nunits; e += nwaves) {
+    const Unit u = units[e];
+    if (filtered_out(filter, u.obj, rows)) continue;
+    const ObjRef d = ragged::load_desc(descs, u.obj);
+    uint32_t m = 0;
+    if constexpr (BYTES) m = mapping[u.obj];
+    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
+    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)d.nvec << 2;
+    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+    unsigned long long* const res = counts + (uint64_t)u.obj * nslots;
+    if (res != t.mism) {
+      t.flush();
+      t.begin(res, first + (uint64_t)u.obj * nslots);
+    }
+    const uint8_t* const ib = in + (d.src_off << 2);
+    const uint8_t* const cb = cmp + (d.dst_off << 2);
+    const uint64_t ishard = d.src_shard << 2, cshard = d.dst_shard << 2;
+    for (uint64_t bw = b0; bw < b1; bw += 64) {
+      // bw is always inside the object; lanes past the last column re-read column bw and never count.
+      const bool ok = bw + lane < b1;
+      const uint64_t col = ok ? bw + lane : bw;
+      auto in_word = [&](uint32_t j) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(ib + (uint64_t)in_idx[j] * ishard + (col << 2));
+        return BYTES ? be(v) ^ m : v;
+      };
+      bool bad = false;
+      for (uint32_t i = 0; i < rows; ++i) {
+        const uint32_t r = apply::wide_dot(coeff + (uint64_t)i * cs, k, in_word);
+        const uint32_t stored = *reinterpret_cast<const uint32_t*>(cb + (uint64_t)out_idx[i] * cshard + (col << 2));
+        bad |= stored != (BYTES ? be(r ^ m) : r);
+      }
+      bad &= ok;
+      if (__ballot(bad)) {
+        uint32_t slot = kNoSlot;
+        if (bad) slot = classify_column<BYTES>(ib, cb, coeff, in_idx, ishard, out_idx, cshard, rows, k, m, col);
+        tally_slots(t, slot, col);
+      }
+    }
+  }
+  t.flush();
+  locate_tails<BYTES>(SLIME_RLOCATE_PASS);
+}
+
+}  // namespace locate
+}  // namespace slime

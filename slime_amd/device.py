@@ -162,11 +162,15 @@ def layout_of(nshards: int, L: int, shard_stride: Optional[int] = None) -> N.Lay
 class Plan:
     """A compiled coefficient matrix on one device (slime_rs_plan_t)."""
 
-    def __init__(self, handle: ctypes.c_void_p, device: int, in_max: int):
+    in_shards = None   # the source shard of each input, when the constructor was told
+    out_shards = None  # the destination shard of each row (None: 0 .. rows - 1)
+
+    def __init__(self, handle: ctypes.c_void_p, device: int, in_max: int, in_shards: Optional[Sequence[int]] = None):
         self._h = handle
         self.device = device
         self.in_max = in_max  # highest source shard index a launch reads
         self.out_max = None   # highest destination shard index (None: rows - 1)
+        self.in_shards = None if in_shards is None else [int(x) for x in in_shards]
         rows, k = ctypes.c_int(), ctypes.c_int()
         N.check(lib.slime_rs_plan_shape(self._h, ctypes.byref(rows), ctypes.byref(k)))
         self.rows, self.k = rows.value, k.value
@@ -175,7 +179,7 @@ class Plan:
     def encode(cls, need: int, total: int, device: int = 0) -> "Plan":
         h = ctypes.c_void_p()
         N.check(lib.slime_rs_plan_encode(device, need, total, ctypes.byref(h)))
-        return cls(h, device, need - 1)
+        return cls(h, device, need - 1, range(need))
 
     @classmethod
     def reconstruct(cls, need: int, total: int, have: Sequence[int], want: Sequence[int], device: int = 0) -> "Plan":
@@ -188,7 +192,7 @@ class Plan:
         hv = (ctypes.c_int * len(have))(*have)
         wv = (ctypes.c_int * len(want))(*want)
         N.check(lib.slime_rs_plan_reconstruct(device, need, total, hv, wv, len(want), ctypes.byref(h)))
-        return cls(h, device, max(have))
+        return cls(h, device, max(have), have)
 
     @classmethod
     def matrix(cls, coeff: np.ndarray, in_shards: Sequence[int], device: int = 0) -> "Plan":
@@ -196,7 +200,7 @@ class Plan:
         h = ctypes.c_void_p()
         sv = (ctypes.c_int * len(in_shards))(*in_shards)
         N.check(lib.slime_rs_plan_matrix(device, c.ctypes.data, c.shape[0], c.shape[1], sv, ctypes.byref(h)))
-        return cls(h, device, max(in_shards))
+        return cls(h, device, max(in_shards), in_shards)
 
     def set_outputs(self, out_shards: Sequence[int]) -> "Plan":
         """Write output row i to destination shard out_shards[i] (e.g. repair in place)."""
@@ -205,6 +209,7 @@ class Plan:
         sv = (ctypes.c_int * len(out_shards))(*out_shards)
         N.check(lib.slime_rs_plan_set_outputs(self._h, sv))
         self.out_max = max(out_shards)
+        self.out_shards = [int(x) for x in out_shards]
         return self
 
     def coefficients(self) -> np.ndarray:
@@ -304,6 +309,46 @@ class Plan:
                                                ctypes.c_void_p(mism.data_ptr()), ctypes.c_void_p(first.data_ptr()),
                                                _stream_handle(self.device, stream)))
         return mism, first
+
+    def locate_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: "Batch", filter: Optional[torch.Tensor] = None,
+                     stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+                     cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """Name the wrong shards of a ragged batch in one launch (slime_rs_plan_locate_batch):
+        addressing as verify_batch.  Returns (counts, first): int64 tensors of shape
+        (batch.nobj, k + rows + 1); counts[o, s] is the number of columns of object o blamed on
+        slot s, first[o, s] the lowest such column or -1.  Slots are the plan's inputs, then its
+        output rows (locate_slots() gives their shard indices), then `unlocated`.  filter: None, or
+        the mismatches tensor of a preceding verify_batch of this plan and batch on the same
+        stream -- objects it shows clean are passed over on the device and keep (0, -1).  Needs
+        rows >= 2 and k + rows <= 63.  Asynchronous; nothing but the two results is written."""
+        for t in (src, cmp):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan's device")
+        if batch.device != self.device or batch.k != self.k:
+            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
+                             f"the plan has k={self.k} on device {self.device}")
+        batch._check_extent(src, src_offset, 0, self.in_max)
+        batch._check_extent(cmp, cmp_offset, 1, self.rows - 1 if self.out_max is None else self.out_max)
+        _check_locate_filter(filter, batch.nobj, self.rows, self.device)
+        counts, first = _verify_results(batch.nobj, self.k + self.rows + 1, self.device)
+        if batch.nobj == 0:
+            return counts, first  # no results: nothing to initialise, nothing to launch
+        N.check(lib.slime_rs_plan_locate_batch(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                                               ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+                                               ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                                               ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                                               _stream_handle(self.device, stream)))
+        return counts, first
+
+    def locate_slots(self) -> list[int]:
+        """The shard index of each of the k + rows slots of locate_batch's results: the plan's
+        input shards, then its output shards (as set_outputs left them)."""
+        if self.in_shards is None:
+            raise ValueError("the plan's input shards are unknown")
+        outs = list(range(self.rows)) if self.out_shards is None else list(self.out_shards)
+        return list(self.in_shards) + outs
 
     @staticmethod
     def _check_extent(t: torch.Tensor, off: int, lay: N.Layout, L: int, nobj: int, max_shard: int) -> None:
@@ -534,6 +579,26 @@ def _verify_results(nobj: int, rows: int, device: int) -> tuple[torch.Tensor, to
             torch.empty(shape, dtype=torch.int64, device=f"cuda:{device}"))
 
 
+def _check_locate_filter(filter: Optional[torch.Tensor], nobj: int, rows: int, device: int) -> None:
+    """locate's filter: the (nobj, rows) int64 mismatches tensor of a verify, on the plan's device."""
+    if filter is None:
+        return
+    if (filter.dtype != torch.int64 or not filter.is_contiguous() or filter.numel() != nobj * rows
+            or _dev_index(filter) != device):
+        raise ValueError(f"filter needs the {nobj} x {rows} contiguous int64 mismatches of a verify on the plan's device")
+
+
+def erasures_from_counts(counts, slots: Sequence[int]) -> list[list[int]]:
+    """Per-object erasure lists from locate's counts (a tensor or an array of shape
+    (nobj, len(slots) + 1)) and Plan.locate_slots(): for each object the sorted shard indices with
+    a non-zero count -- what PlanSet.for_erasures takes.  The last column (`unlocated`) names no
+    shard and is not looked at: check it before trusting a repair."""
+    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    if c.ndim != 2 or c.shape[1] != len(slots) + 1:
+        raise ValueError(f"counts needs shape (nobj, {len(slots) + 1}) for {len(slots)} slots")
+    return [sorted(int(slots[s]) for s in np.nonzero(row[:-1])[0]) for row in c]
+
+
 def fill_symbols(t: torch.Tensor, seed: int, stream: Optional[torch.cuda.Stream] = None) -> None:
     """Deterministic synthetic symbols in [0, p) — word g is a function of (seed, g)."""
     dev = _dev_index(t)
@@ -736,6 +801,27 @@ def verify_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batc
                  ctypes.c_void_p(mapping.data_ptr()), ctypes.c_void_p(mism.data_ptr()),
                  ctypes.c_void_p(first.data_ptr()), _stream_handle(plan_or_set.device, stream)))
     return mism, first
+
+
+def locate_objects_batch(plan: Plan, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, mapping: torch.Tensor,
+                         filter: Optional[torch.Tensor] = None,
+                         stream: Optional[torch.cuda.Stream] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Plan.locate_batch over a ragged batch of stored chunks (slime_rs_locate_objects_batch):
+    symbol = BE(word) ^ mapping[o], addressing and checks as verify_objects_batch with a Plan.
+    Returns (counts, first) of shape (batch.nobj, k + rows + 1) exactly as Plan.locate_batch;
+    filter is the mismatches tensor of a preceding verify_objects_batch, or None."""
+    if _check_objects_batch("locate_objects_batch", plan, src, cmp, batch, mapping):
+        raise ValueError("locate_objects_batch takes a Plan, not a PlanSet")
+    _check_locate_filter(filter, batch.nobj, plan.rows, plan.device)
+    counts, first = _verify_results(batch.nobj, plan.k + plan.rows + 1, plan.device)
+    if batch.nobj == 0:
+        return counts, first  # no results: nothing to initialise, nothing to launch
+    N.check(lib.slime_rs_locate_objects_batch(plan._h, batch._h, ctypes.c_void_p(src.data_ptr()),
+                                              ctypes.c_void_p(cmp.data_ptr()), ctypes.c_void_p(mapping.data_ptr()),
+                                              ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                                              ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                                              _stream_handle(plan.device, stream)))
+    return counts, first
 
 
 # ---- ragged byte encode: objects of different sizes ingested in one launch ----
