@@ -509,14 +509,57 @@ int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch
  * Forms: k <= 16 over 4-byte aligned src and cmp runs four columns a lane,
  * anything else one column a lane (correct, not fast).  Out of scope:
  * uniform-layout entry points (a uniform batch is a packed batch of equal
- * lengths), plan-set locate, matrix-core forms and k + rows > 63, correcting
- * more than one wrong shard per column, device digests. */
+ * lengths), matrix-core forms and k + rows > 63, correcting more than one
+ * wrong shard per column, device digests.  Plan-set locate is below. */
 int slime_rs_plan_locate_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
                                const uint32_t *cmp, const uint64_t *filter, uint64_t *counts, uint64_t *first,
                                void *stream);
 int slime_rs_locate_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t *src,
                                   const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
                                   uint64_t *counts, uint64_t *first, void *stream);
+
+/* ---- plan-set locate: name the corrupt shards of degraded objects ---------------
+ * The two calls above with a set in place of the plan, as
+ * slime_rs_planset_verify_batch is to slime_rs_plan_verify_batch: object o of
+ * a PLANNED batch is classified with its own plan of the set -- its own k input
+ * shard indices, its own rows_o coefficient rows and its own output shard
+ * indices.  A degraded object (a chunk missing, a disk out) cannot be checked
+ * against the encode plan, whose slots include the absent shard; its own plan
+ * reads k present shards and checks the other present ones, so scrub
+ * (slime_rs_planset_verify_batch), locate and repair stay on the device.
+ * SLIME_RS_NO_PLAN objects and L == 0 objects keep the initial values.
+ * Results: two device arrays of nobj x (k + max_rows + 1) uint64, max_rows the
+ * set's (slime_rs_planset_info), initialised by the call as above.  For object
+ * o, slot j < k is its plan's input j, slot k + i for i < rows_o its output row
+ * i; slots k + rows_o .. k + max_rows - 1 keep (0, UINT64_MAX); `unlocated` is
+ * ALWAYS slot k + max_rows, so one column of the result means the same thing
+ * for every object.
+ * The rule is the one above with the object's own plan, and one addition: an
+ * object whose plan has rows_o < 2 reports every mismatching column as
+ * unlocated (one row cannot tell an input from its output).  A set may hold
+ * such plans next to better ones, so this is an answer per object, not a
+ * refusal.
+ * filter: NULL, or the `mismatches` array of a preceding
+ * slime_rs_planset_verify_batch / _verify_objects_batch of the same set and
+ * batch on the stream (nobj x max_rows; rows past an object's own are zero by
+ * that call's contract).  An object whose max_rows entries are all zero is
+ * passed over before any load of its data.
+ * Asynchronous, no scratch, a static walk in every schedule and pipeline mode,
+ * no counter set, capturable.  A set carries no launched mark.
+ * SLIME_RS_ERR_INVALID_ARG, checked in this order: a null set or batch, a batch
+ * that is not planned or was planned for another plan count, k or device;
+ * max_rows < 2 (no object of the set could be located); k + max_rows > 63; null
+ * result arrays; null buffers; for the byte form a null mapping.
+ * Forms as above (k <= 16 over 4-byte aligned bases: four columns a lane; else
+ * one column a lane).  Out of scope: matrix-core forms, k + max_rows > 63, more
+ * than one wrong shard per column, a register-resident rare path, device
+ * digests. */
+int slime_rs_planset_locate_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src,
+                                  const uint32_t *cmp, const uint64_t *filter, uint64_t *counts,
+                                  uint64_t *first, void *stream);
+int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
+                                          const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
+                                          uint64_t *counts, uint64_t *first, void *stream);
 
 /* ---- ragged byte encode: ingest objects of different sizes in one launch -------
  * slime_rs_encode_objects over the spans of a batch, each object with its own

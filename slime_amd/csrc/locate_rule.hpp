@@ -74,7 +74,26 @@ struct Column {
     if (cand != 0 && (cand & (cand - 1)) == 0) return (uint32_t)__builtin_ctzll(cand);
     return k + rows;
   }
+  // The slot in a plan SET's result row (set_slot below): this column's plan has `rows` rows,
+  // the set's widest has max_rows.
+  __host__ __device__ __forceinline__ uint32_t slot_in_set(uint32_t k, uint32_t rows, uint32_t max_rows) const;
 };
+
+// A plan set's result row has k + max_rows + 1 slots for every object, whatever its own plan's
+// row count: inputs and rows keep slot()'s numbers, `unlocated` is always slot k + max_rows (one
+// column of the result means the same for every object), slots k + rows .. k + max_rows - 1 are
+// never named.  `slot` is Column::slot(k, rows) of the object's own plan.  A plan of ONE row
+// cannot tell an input from its output -- slot() would name the row -- so every mismatching
+// column of such an object is unlocated: the answer is per object, where the single-plan entry
+// point refuses rows < 2 outright.
+__host__ __device__ __forceinline__ uint32_t set_slot(uint32_t slot, uint32_t k, uint32_t rows, uint32_t max_rows) {
+  if (slot == kNoSlot) return kNoSlot;
+  if (rows < 2 || slot == k + rows) return k + max_rows;
+  return slot;
+}
+__host__ __device__ __forceinline__ uint32_t Column::slot_in_set(uint32_t k, uint32_t rows, uint32_t max_rows) const {
+  return set_slot(slot(k, rows), k, rows, max_rows);
+}
 
 }  // namespace locate
 }  // namespace slime

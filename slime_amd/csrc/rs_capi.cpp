@@ -911,6 +911,51 @@ int slime_rs_locate_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, 
   return 0;
 }
 
+// ---- plan-set locate (rs_locate_planset.hip) ----------------------------------------
+
+// What both plan-set locate forms check after check_batch_set, symbols or bytes, in this order.
+static int check_locate_set(const char* what, const slime_rs_planset* set, const void* src, const void* cmp,
+                            const uint64_t* counts, const uint64_t* first) {
+  if (set->max_rows < 2)
+    return fail(Status::InvalidArg, std::string(what) + ": no plan of the set has more than " +
+                                        std::to_string(set->max_rows) +
+                                        " row: one parity row cannot tell which shard is wrong");
+  if (set->k + set->max_rows > 63)
+    return fail(Status::InvalidArg, std::string(what) + ": k + max_rows = " + std::to_string(set->k + set->max_rows) +
+                                        " exceeds 63 (a wave's tally keeps one slot per lane)");
+  if (!counts || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  return 0;
+}
+
+int slime_rs_planset_locate_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src,
+                                  const uint32_t* cmp, const uint64_t* filter, uint64_t* counts, uint64_t* first,
+                                  void* stream) {
+  if (int rc = check_batch_set("planset_locate_batch", set, batch)) return rc;
+  if (int rc = check_locate_set("planset_locate_batch", set, src, cmp, counts, first)) return rc;
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), nullptr, filter, counts, first};
+  v.p.rows = set->max_rows;  // the result arrays' and the filter's row stride
+  DeviceScope ds(set->device);
+  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
+                                          const uint8_t* cmp, const uint32_t* mapping, const uint64_t* filter,
+                                          uint64_t* counts, uint64_t* first, void* stream) {
+  if (int rc = check_batch_set("planset_locate_objects_batch", set, batch)) return rc;
+  if (int rc = check_locate_set("planset_locate_objects_batch", set, src, cmp, counts, first)) return rc;
+  // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
+  if (!mapping) return fail(Status::InvalidArg, "planset_locate_objects_batch: null mapping");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), mapping, filter, counts, first};
+  v.p.rows = set->max_rows;
+  DeviceScope ds(set->device);
+  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
   if (!plan || !out_shards) return fail(Status::InvalidArg, "plan_set_outputs: bad args");
   // The table rewrite below is a synchronous copy that nothing orders against

@@ -112,6 +112,7 @@ hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t s) {
   // The vector kernels are instantiated with the geometry of their K: the tables must be cut by it.
   if (vec && (v.w.U != ragged::unroll_for_k((int)v.w.k) || v.w.C != ragged::unit_tiles_for_k((int)v.w.k)))
     return hipErrorInvalidValue;
+  if (v.p.table) return launch_locate_planset(v, s);  // every object with its own plan of a set
   if (!vec) return launch_columns(v, s);
   return ragged::with_k(v.w.k, [&](auto kc) { return launch_rows<decltype(kc)::value>(v, s); });
 }

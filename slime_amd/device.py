@@ -476,6 +476,9 @@ class PlanSet:
         N.check(lib.slime_rs_planset_info(self._h, ctypes.byref(n), ctypes.byref(k), ctypes.byref(r),
                                           ctypes.byref(i), ctypes.byref(o)))
         self.nplans, self.k, self.max_rows, self.in_max, self.out_max = n.value, k.value, r.value, i.value, o.value
+        # Each member's (input shards or None, output shards, rows), for locate_slots.
+        self._members = [(None if p.in_shards is None else list(p.in_shards),
+                          list(range(p.rows)) if p.out_shards is None else list(p.out_shards), p.rows) for p in plans]
 
     @classmethod
     def for_erasures(cls, need: int, total: int, patterns, device: int = 0) -> tuple["PlanSet", np.ndarray]:
@@ -560,6 +563,87 @@ class PlanSet:
                                                   _stream_handle(self.device, stream)))
         return mism, first
 
+    @classmethod
+    def for_scrub(cls, need: int, total: int, missing, device: int = 0) -> tuple["PlanSet", np.ndarray]:
+        """One scrub plan per DISTINCT pattern of absent shards: missing[o] lists the shards object o
+        does not have (empty or None: all present, which is a plan too).  Each plan reads the first
+        `need` present shards in index order and checks the remaining present ones -- always parity
+        rows, the highest present indices, at most total - need - len(missing[o]) of them.  An
+        object with exactly `need` present shards has nothing to check and gets N.NO_PLAN; fewer is
+        a ValueError.  Returns the set and the per-object plan indices (uint32) for
+        Batch(..., plans=...), to verify_batch and locate_batch degraded objects from their own
+        survivors."""
+        index: dict = {}
+        plan_of = np.full(len(missing), N.NO_PLAN, dtype=np.uint32)
+        for o, pat in enumerate(missing):
+            key = tuple(sorted(set(int(x) for x in pat))) if pat is not None else ()
+            if key and (key[0] < 0 or key[-1] >= total):
+                raise ValueError(f"object {o}: missing shards {key} are not shards of a {need}/{total} code")
+            if total - len(key) < need:
+                raise ValueError(f"object {o}: missing shards {key} leave fewer than {need} of {total} shards")
+            if total - len(key) == need:
+                continue  # nothing left to check
+            plan_of[o] = index.setdefault(key, len(index))
+        if not index:
+            raise ValueError("no object has a shard left to check: nothing to scrub")
+        plans = []
+        try:
+            for key in index:  # insertion order: plan i is pattern i
+                present = [i for i in range(total) if i not in key]
+                have, want = present[:need], present[need:]
+                plans.append(Plan.reconstruct(need, total, have, want, device).set_outputs(want))
+            return cls(plans), plan_of
+        finally:
+            for p in plans:
+                p.close()
+
+    def locate_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, filter: Optional[torch.Tensor] = None,
+                     stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+                     cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """Plan.locate_batch with every object classified by its own plan of the set
+        (slime_rs_planset_locate_batch): a degraded object is located from its own survivor set.
+        Returns (counts, first) of shape (batch.nobj, k + max_rows + 1): for object o, slot j < k is
+        its plan's input j, slot k + i its output row i (locate_slots(plan) gives the shard indices),
+        slots past its plan's rows keep (0, -1), and `unlocated` is always the last column.  An
+        object whose plan has one row reports every mismatching column as unlocated.  filter: None,
+        or the mismatches tensor of a preceding PlanSet.verify_batch of this set and batch on the
+        same stream.  Needs max_rows >= 2 and k + max_rows <= 63.  Asynchronous; nothing but the
+        two results is written."""
+        for t in (src, cmp):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+            if _dev_index(t) != self.device:
+                raise ValueError("tensor is not on the plan set's device")
+        if getattr(batch, "plans", None) is None:
+            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
+        if batch.device != self.device or batch.k != self.k or batch.nplans != self.nplans:
+            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
+                             f"the set has {self.nplans} plans of k={self.k} on device {self.device}")
+        # The set-wide highest shard indices: every object is checked as if it ran the widest plan.
+        batch._check_extent(src, src_offset, 0, self.in_max)
+        batch._check_extent(cmp, cmp_offset, 1, self.out_max)
+        _check_locate_filter(filter, batch.nobj, self.max_rows, self.device)
+        counts, first = _verify_results(batch.nobj, self.k + self.max_rows + 1, self.device)
+        if batch.nobj == 0:
+            return counts, first  # no results: nothing to initialise, nothing to launch
+        N.check(lib.slime_rs_planset_locate_batch(self._h, batch._h,
+                                                  ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                                                  ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+                                                  ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                                                  ctypes.c_void_p(counts.data_ptr()),
+                                                  ctypes.c_void_p(first.data_ptr()),
+                                                  _stream_handle(self.device, stream)))
+        return counts, first
+
+    def locate_slots(self, i: int) -> list:
+        """The shard index of each of the k + max_rows slots of locate_batch's results for an object
+        on plan i: the plan's input shards, its output shards, then None for the slots past its
+        rows (they are never named)."""
+        ins, outs, rows = self._members[i]
+        if ins is None:
+            raise ValueError(f"plan {i}'s input shards are unknown")
+        return list(ins) + list(outs) + [None] * (self.max_rows - rows)
+
     def close(self) -> None:
         if self._h:
             lib.slime_rs_planset_destroy(self._h)  # waits for the device (hipFree)
@@ -597,6 +681,34 @@ def erasures_from_counts(counts, slots: Sequence[int]) -> list[list[int]]:
     if c.ndim != 2 or c.shape[1] != len(slots) + 1:
         raise ValueError(f"counts needs shape (nobj, {len(slots) + 1}) for {len(slots)} slots")
     return [sorted(int(slots[s]) for s in np.nonzero(row[:-1])[0]) for row in c]
+
+
+def erasures_from_set_counts(counts, plan_set: "PlanSet", plan_of, missing=None) -> list[list[int]]:
+    """erasures_from_counts for PlanSet.locate_batch's counts (shape (nobj, k + max_rows + 1)): for
+    each object the sorted shard indices with a non-zero count, mapped through the slots of that
+    object's own plan (plan_of[o]; N.NO_PLAN objects name nothing) and united with missing[o], the
+    shards it was already known to lack -- what PlanSet.for_erasures takes.  The last column
+    (`unlocated`) names no shard and is not looked at: check it before trusting a repair."""
+    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    nslots = plan_set.k + plan_set.max_rows
+    if c.ndim != 2 or c.shape[1] != nslots + 1 or c.shape[0] != len(plan_of):
+        raise ValueError(f"counts needs shape ({len(plan_of)}, {nslots + 1}) for {nslots} slots")
+    if missing is not None and len(missing) != len(plan_of):
+        raise ValueError(f"missing needs one entry per object ({len(plan_of)})")
+    out = []
+    for o, row in enumerate(c):
+        bad = set(int(x) for x in missing[o]) if missing is not None and missing[o] is not None else set()
+        hits = np.nonzero(row[:-1])[0]
+        if len(hits):
+            if int(plan_of[o]) == N.NO_PLAN:
+                raise ValueError(f"object {o} has no plan but non-zero counts")
+            slots = plan_set.locate_slots(int(plan_of[o]))
+            for s in hits:
+                if slots[s] is None:
+                    raise ValueError(f"object {o}: slot {int(s)} is past its plan's rows but has a count")
+                bad.add(int(slots[s]))
+        out.append(sorted(bad))
+    return out
 
 
 def fill_symbols(t: torch.Tensor, seed: int, stream: Optional[torch.cuda.Stream] = None) -> None:
@@ -803,24 +915,27 @@ def verify_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batc
     return mism, first
 
 
-def locate_objects_batch(plan: Plan, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, mapping: torch.Tensor,
+def locate_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, mapping: torch.Tensor,
                          filter: Optional[torch.Tensor] = None,
                          stream: Optional[torch.cuda.Stream] = None) -> tuple[torch.Tensor, torch.Tensor]:
-    """Plan.locate_batch over a ragged batch of stored chunks (slime_rs_locate_objects_batch):
-    symbol = BE(word) ^ mapping[o], addressing and checks as verify_objects_batch with a Plan.
-    Returns (counts, first) of shape (batch.nobj, k + rows + 1) exactly as Plan.locate_batch;
-    filter is the mismatches tensor of a preceding verify_objects_batch, or None."""
-    if _check_objects_batch("locate_objects_batch", plan, src, cmp, batch, mapping):
-        raise ValueError("locate_objects_batch takes a Plan, not a PlanSet")
-    _check_locate_filter(filter, batch.nobj, plan.rows, plan.device)
-    counts, first = _verify_results(batch.nobj, plan.k + plan.rows + 1, plan.device)
+    """Plan.locate_batch over a ragged batch of stored chunks (slime_rs_locate_objects_batch; with
+    a PlanSet and a planned batch every object takes its own plan,
+    slime_rs_planset_locate_objects_batch): symbol = BE(word) ^ mapping[o], addressing and checks
+    as verify_objects_batch.  Returns (counts, first) of shape (batch.nobj, k + rows + 1) exactly
+    as Plan.locate_batch, or (batch.nobj, k + max_rows + 1) as PlanSet.locate_batch; filter is the
+    mismatches tensor of a preceding verify_objects_batch with the same plan or set, or None."""
+    is_set = _check_objects_batch("locate_objects_batch", plan_or_set, src, cmp, batch, mapping)
+    rows = plan_or_set.max_rows if is_set else plan_or_set.rows
+    _check_locate_filter(filter, batch.nobj, rows, plan_or_set.device)
+    counts, first = _verify_results(batch.nobj, plan_or_set.k + rows + 1, plan_or_set.device)
     if batch.nobj == 0:
         return counts, first  # no results: nothing to initialise, nothing to launch
-    N.check(lib.slime_rs_locate_objects_batch(plan._h, batch._h, ctypes.c_void_p(src.data_ptr()),
-                                              ctypes.c_void_p(cmp.data_ptr()), ctypes.c_void_p(mapping.data_ptr()),
-                                              ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
-                                              ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
-                                              _stream_handle(plan.device, stream)))
+    call = lib.slime_rs_planset_locate_objects_batch if is_set else lib.slime_rs_locate_objects_batch
+    N.check(call(plan_or_set._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(cmp.data_ptr()),
+                 ctypes.c_void_p(mapping.data_ptr()),
+                 ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                 ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                 _stream_handle(plan_or_set.device, stream)))
     return counts, first
 
 
