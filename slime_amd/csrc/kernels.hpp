@@ -405,7 +405,7 @@ hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStrea
 // Needs 2 <= rows and k + rows <= 63.  The launch initialises both result
 // arrays with rs_verify_init_kernel whenever w.nobj > 0, writes nothing else
 // and uses no scratch; a static walk in every schedule mode.
-//   a set (p.table != nullptr, rs_locate_planset.hip): object o is classified with its own plan;
+//   a set (p.table != nullptr, the SET forms): object o is classified with its own plan;
 //     p.rows is the set's max_rows, the filter is nobj x max_rows, the results are
 //     nobj x (k + max_rows + 1) with `unlocated` at slot k + max_rows for every object, and
 //     slots k + rows_o .. k + max_rows - 1 keep their initial values.  An object whose plan has
@@ -422,9 +422,6 @@ struct RaggedLocateLaunch {
   uint64_t* first;
 };
 hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t stream);
-// The planned kernels' launch alone (launch_locate_ragged calls it after its checks and the
-// results' initialisation).
-hipError_t launch_locate_planset(const RaggedLocateLaunch& v, hipStream_t stream);
 
 // --- ragged byte encode (rs_bytes_ragged_encode.hip) ------------------------------
 // The fused byte encode over a ragged batch: object o of sizes[o] bytes, its k

@@ -27,6 +27,7 @@
 #include <random>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "capi_internal.hpp"
@@ -597,8 +598,15 @@ int slime_rs_batch_destroy(slime_rs_batch_t batch) {
   return 0;
 }
 
+}  // extern "C"
+namespace {
+
+// ---- ragged launches: one plan, or a plan set over a planned batch ------------------
+// Every launch kind is written once below, over the handle type H (slime_rs_plan or
+// slime_rs_planset); the entry points pass their own name for the messages.
+
 // What every batch entry point checks first, in this order; `what` names the entry point.
-static int check_batch_plan(const char* what, const slime_rs_plan* plan, const slime_rs_batch* batch) {
+int check_batch(const char* what, const slime_rs_plan* plan, const slime_rs_batch* batch) {
   if (!plan) return fail(Status::InvalidArg, std::string(what) + ": null plan");
   if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
   if (plan->k != batch->k || plan->device != batch->device)
@@ -607,8 +615,7 @@ static int check_batch_plan(const char* what, const slime_rs_plan* plan, const s
                                         std::to_string(plan->k) + " on device " + std::to_string(plan->device));
   return 0;
 }
-
-static int check_batch_set(const char* what, const slime_rs_planset* set, const slime_rs_batch* batch) {
+int check_batch(const char* what, const slime_rs_planset* set, const slime_rs_batch* batch) {
   if (!set) return fail(Status::InvalidArg, std::string(what) + ": null set");
   if (!batch) return fail(Status::InvalidArg, std::string(what) + ": null batch");
   if (!batch->planned)
@@ -623,11 +630,11 @@ static int check_batch_set(const char* what, const slime_rs_planset* set, const 
   return 0;
 }
 
-static bool batch_has_work(const slime_rs_batch* batch) { return batch->counts.units != 0 || batch->counts.tails != 0; }
+bool batch_has_work(const slime_rs_batch* batch) { return batch->counts.units != 0 || batch->counts.tails != 0; }
 
 // The batch's side of a ragged launch over the buffers a and b (the vector
 // kernels need both 4-byte aligned, as slime_rs_plan_execute).
-static RaggedWork batch_work(const slime_rs_batch* batch, const void* a, const void* b) {
+RaggedWork batch_work(const slime_rs_batch* batch, const void* a, const void* b) {
   RaggedWork w;
   w.desc = batch->d_desc;
   w.units = batch->d_units;
@@ -644,7 +651,7 @@ static RaggedWork batch_work(const slime_rs_batch* batch, const void* a, const v
 
 // The plan's side: one plan for every object, or a set's table (rows: the
 // verify launches set the result arrays' row stride themselves).
-static RaggedPlan plan_side(const slime_rs_plan* plan) {
+RaggedPlan plan_side(const slime_rs_plan* plan) {
   RaggedPlan p;
   p.coeff = plan->d_coeff;
   p.in_idx = plan->d_in_idx;
@@ -652,22 +659,128 @@ static RaggedPlan plan_side(const slime_rs_plan* plan) {
   p.rows = plan->rows;
   return p;
 }
-static RaggedPlan plan_side(const slime_rs_planset* set) {
+RaggedPlan plan_side(const slime_rs_planset* set) {
   RaggedPlan p;
   p.table = set->d_table;
   return p;
 }
 
-int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
-                                void* stream) {
-  if (int rc = check_batch_plan("plan_execute_batch", plan, batch)) return rc;
+
+// The rows of a verify's or locate's result arrays (and of a locate's filter): a set's widest plan's.
+uint32_t result_rows(const slime_rs_plan* plan) { return plan->rows; }
+uint32_t result_rows(const slime_rs_planset* set) { return set->max_rows; }
+
+// Every launch reads the plan's output table: slime_rs_plan_set_outputs refuses from here on.  A
+// set holds a snapshot of its own.
+void mark_launched(slime_rs_plan* plan) { plan->executed.store(true, std::memory_order_relaxed); }
+void mark_launched(slime_rs_planset*) {}
+
+template <class H>
+int execute_batch(const char* what, H* h, slime_rs_batch* batch, const uint32_t* src, uint32_t* dst, void* stream) {
+  if (int rc = check_batch(what, h, batch)) return rc;
   if (!batch_has_work(batch)) return 0;  // an empty batch
-  if (!src || !dst) return fail(Status::InvalidArg, "plan_execute_batch: null buffer");
-  const RaggedLaunch a{src, dst, batch_work(batch, src, dst), plan_side(plan)};
-  plan->executed.store(true, std::memory_order_relaxed);
-  DeviceScope ds(plan->device);
+  if (!src || !dst) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  const RaggedLaunch a{src, dst, batch_work(batch, src, dst), plan_side(h)};
+  mark_launched(h);
+  DeviceScope ds(h->device);
   HIP_TRY(launch_apply_ragged(a, (hipStream_t)stream));
   return 0;
+}
+
+// What both verify forms check next, symbols or bytes (a null mapping is the byte entry points' own check).
+int check_verify_batch(const char* what, const void* src, const void* cmp, const uint64_t* mismatches,
+                       const uint64_t* first) {
+  if (!mismatches || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  return 0;
+}
+
+template <class H>
+int verify_batch(const char* what, H* h, slime_rs_batch* batch, const uint32_t* src, const uint32_t* cmp,
+                 uint64_t* mismatches, uint64_t* first, void* stream) {
+  if (int rc = check_batch(what, h, batch)) return rc;
+  if (int rc = check_verify_batch(what, src, cmp, mismatches, first)) return rc;
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  RaggedVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(h), mismatches, first};
+  v.p.rows = result_rows(h);  // the result arrays' row stride
+  mark_launched(h);
+  DeviceScope ds(h->device);
+  HIP_TRY(launch_verify_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+// The ragged launches over stored chunk bytes (rs_bytes_ragged.hip); validation as their symbol twins.
+template <class H>
+int decode_objects_batch(const char* what, H* h, slime_rs_batch* batch, const uint8_t* src, uint8_t* dst,
+                         const uint32_t* mapping, void* stream) {
+  if (int rc = check_batch(what, h, batch)) return rc;
+  if (!batch_has_work(batch)) return 0;  // an empty batch
+  if (!src || !dst) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  if (!mapping) return fail(Status::InvalidArg, std::string(what) + ": null mapping");
+  const RaggedBytesLaunch a{src, dst, batch_work(batch, src, dst), plan_side(h), mapping};
+  mark_launched(h);
+  DeviceScope ds(h->device);
+  HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
+  return 0;
+}
+
+template <class H>
+int verify_objects_batch(const char* what, H* h, slime_rs_batch* batch, const uint8_t* src, const uint8_t* cmp,
+                         const uint32_t* mapping, uint64_t* mismatches, uint64_t* first, void* stream) {
+  if (int rc = check_batch(what, h, batch)) return rc;
+  if (int rc = check_verify_batch(what, src, cmp, mismatches, first)) return rc;
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  // An empty batch launches only the initialisation, which reads no mapping.
+  if (!mapping && batch_has_work(batch)) return fail(Status::InvalidArg, std::string(what) + ": null mapping");
+  RaggedBytesVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(h), mapping, mismatches, first};
+  v.p.rows = result_rows(h);  // the result arrays' row stride
+  mark_launched(h);
+  DeviceScope ds(h->device);
+  HIP_TRY(launch_verify_bytes_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+// What the locate forms check after check_batch, symbols or bytes, in this order; rows: result_rows.
+int check_locate_batch(const char* what, bool set, uint32_t k, uint32_t rows, const void* src, const void* cmp,
+                       const uint64_t* counts, const uint64_t* first) {
+  if (rows < 2)
+    return fail(Status::InvalidArg, std::string(what) +
+                                        (set ? ": no plan of the set has more than " : ": the plan has ") +
+                                        std::to_string(rows) + " row: one parity row cannot tell which shard is wrong");
+  if (k + rows > 63)
+    return fail(Status::InvalidArg, std::string(what) + (set ? ": k + max_rows = " : ": k + rows = ") +
+                                        std::to_string(k + rows) +
+                                        " exceeds 63 (a wave's tally keeps one slot per lane)");
+  if (!counts || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
+  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
+  return 0;
+}
+
+// Ragged locate (rs_locate_ragged.hip), symbols (bytes = false, no mapping) or stored chunk bytes.
+template <class H>
+int locate_batch(const char* what, H* h, slime_rs_batch* batch, const void* src, const void* cmp, bool bytes,
+                 const uint32_t* mapping, const uint64_t* filter, uint64_t* counts, uint64_t* first, void* stream) {
+  if (int rc = check_batch(what, h, batch)) return rc;
+  if (int rc = check_locate_batch(what, std::is_same<H, slime_rs_planset>::value, h->k, result_rows(h), src, cmp,
+                                  counts, first))
+    return rc;
+  // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
+  if (bytes && !mapping) return fail(Status::InvalidArg, std::string(what) + ": null mapping");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(h), mapping, filter, counts, first};
+  v.p.rows = result_rows(h);  // the result arrays' and the filter's row stride
+  mark_launched(h);
+  DeviceScope ds(h->device);
+  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
+}  // namespace
+extern "C" {
+
+int slime_rs_plan_execute_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
+                                void* stream) {
+  return execute_batch("plan_execute_batch", plan, batch, src, dst, stream);
 }
 
 // ---- plan sets (planset_table.hpp; the planned kernels of rs_ragged.hip) ----------
@@ -737,13 +850,7 @@ int slime_rs_planset_destroy(slime_rs_planset_t set) {
 
 int slime_rs_planset_execute_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src, uint32_t* dst,
                                    void* stream) {
-  if (int rc = check_batch_set("planset_execute_batch", set, batch)) return rc;
-  if (!batch_has_work(batch)) return 0;  // an empty batch
-  if (!src || !dst) return fail(Status::InvalidArg, "planset_execute_batch: null buffer");
-  const RaggedLaunch a{src, dst, batch_work(batch, src, dst), plan_side(set)};
-  DeviceScope ds(set->device);
-  HIP_TRY(launch_apply_ragged(a, (hipStream_t)stream));
-  return 0;
+  return execute_batch("planset_execute_batch", set, batch, src, dst, stream);
 }
 
 // Shared by both verify entry points: the result arrays and the object count.
@@ -775,185 +882,64 @@ int slime_rs_plan_verify(slime_rs_plan_t plan, const uint32_t* src, slime_rs_lay
 
 // ---- ragged verify (rs_verify_ragged.hip) ------------------------------------------
 
-// What both verify forms check next, symbols or bytes (a null mapping is the byte entry points' own check).
-static int check_verify_batch(const char* what, const void* src, const void* cmp, const uint64_t* mismatches,
-                              const uint64_t* first) {
-  if (!mismatches || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
-  return 0;
-}
-
 int slime_rs_plan_verify_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, const uint32_t* cmp,
                                uint64_t* mismatches, uint64_t* first, void* stream) {
-  if (int rc = check_batch_plan("plan_verify_batch", plan, batch)) return rc;
-  if (int rc = check_verify_batch("plan_verify_batch", src, cmp, mismatches, first)) return rc;
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  const RaggedVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), mismatches, first};
-  // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
-  plan->executed.store(true, std::memory_order_relaxed);
-  DeviceScope ds(plan->device);
-  HIP_TRY(launch_verify_ragged(v, (hipStream_t)stream));
-  return 0;
+  return verify_batch("plan_verify_batch", plan, batch, src, cmp, mismatches, first, stream);
 }
 
 int slime_rs_planset_verify_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src,
                                   const uint32_t* cmp, uint64_t* mismatches, uint64_t* first, void* stream) {
-  if (int rc = check_batch_set("planset_verify_batch", set, batch)) return rc;
-  if (int rc = check_verify_batch("planset_verify_batch", src, cmp, mismatches, first)) return rc;
-  if (batch->counts.nobj == 0) return 0;
-  RaggedVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), mismatches, first};
-  v.p.rows = set->max_rows;  // the result arrays' row stride
-  DeviceScope ds(set->device);
-  HIP_TRY(launch_verify_ragged(v, (hipStream_t)stream));
-  return 0;
+  return verify_batch("planset_verify_batch", set, batch, src, cmp, mismatches, first, stream);
 }
 
 // ---- ragged byte objects (rs_bytes_ragged.hip) --------------------------------------
-// The four ragged launches over stored chunk bytes; validation as their symbol twins.
 
 int slime_rs_decode_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src, uint8_t* dst,
                                   const uint32_t* mapping, void* stream) {
-  if (int rc = check_batch_plan("decode_objects_batch", plan, batch)) return rc;
-  if (!batch_has_work(batch)) return 0;  // an empty batch
-  if (!src || !dst) return fail(Status::InvalidArg, "decode_objects_batch: null buffer");
-  if (!mapping) return fail(Status::InvalidArg, "decode_objects_batch: null mapping");
-  const RaggedBytesLaunch a{src, dst, batch_work(batch, src, dst), plan_side(plan), mapping};
-  plan->executed.store(true, std::memory_order_relaxed);
-  DeviceScope ds(plan->device);
-  HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
-  return 0;
+  return decode_objects_batch("decode_objects_batch", plan, batch, src, dst, mapping, stream);
 }
 
 int slime_rs_planset_decode_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
                                           uint8_t* dst, const uint32_t* mapping, void* stream) {
-  if (int rc = check_batch_set("planset_decode_objects_batch", set, batch)) return rc;
-  if (!batch_has_work(batch)) return 0;  // an empty batch
-  if (!src || !dst) return fail(Status::InvalidArg, "planset_decode_objects_batch: null buffer");
-  if (!mapping) return fail(Status::InvalidArg, "planset_decode_objects_batch: null mapping");
-  const RaggedBytesLaunch a{src, dst, batch_work(batch, src, dst), plan_side(set), mapping};
-  DeviceScope ds(set->device);
-  HIP_TRY(launch_decode_bytes_ragged(a, (hipStream_t)stream));
-  return 0;
+  return decode_objects_batch("planset_decode_objects_batch", set, batch, src, dst, mapping, stream);
 }
 
 int slime_rs_verify_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src,
                                   const uint8_t* cmp, const uint32_t* mapping, uint64_t* mismatches, uint64_t* first,
                                   void* stream) {
-  if (int rc = check_batch_plan("verify_objects_batch", plan, batch)) return rc;
-  if (int rc = check_verify_batch("verify_objects_batch", src, cmp, mismatches, first)) return rc;
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  // An empty batch launches only the initialisation, which reads no mapping.
-  if (!mapping && batch_has_work(batch)) return fail(Status::InvalidArg, "verify_objects_batch: null mapping");
-  const RaggedBytesVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), mapping, mismatches, first};
-  // A verify reads the plan's output table like any launch (slime_rs_plan_set_outputs).
-  plan->executed.store(true, std::memory_order_relaxed);
-  DeviceScope ds(plan->device);
-  HIP_TRY(launch_verify_bytes_ragged(v, (hipStream_t)stream));
-  return 0;
+  return verify_objects_batch("verify_objects_batch", plan, batch, src, cmp, mapping, mismatches, first, stream);
 }
 
 int slime_rs_planset_verify_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
                                           const uint8_t* cmp, const uint32_t* mapping, uint64_t* mismatches,
                                           uint64_t* first, void* stream) {
-  if (int rc = check_batch_set("planset_verify_objects_batch", set, batch)) return rc;
-  if (int rc = check_verify_batch("planset_verify_objects_batch", src, cmp, mismatches, first)) return rc;
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  // An empty batch launches only the initialisation, which reads no mapping.
-  if (!mapping && batch_has_work(batch)) return fail(Status::InvalidArg, "planset_verify_objects_batch: null mapping");
-  RaggedBytesVerifyLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), mapping, mismatches, first};
-  v.p.rows = set->max_rows;  // the result arrays' row stride
-  DeviceScope ds(set->device);
-  HIP_TRY(launch_verify_bytes_ragged(v, (hipStream_t)stream));
-  return 0;
+  return verify_objects_batch("planset_verify_objects_batch", set, batch, src, cmp, mapping, mismatches, first, stream);
 }
 
 // ---- ragged locate (rs_locate_ragged.hip) -------------------------------------------
 
-// What both locate forms check after check_batch_plan, symbols or bytes, in this order.
-static int check_locate_batch(const char* what, const slime_rs_plan* plan, const void* src, const void* cmp,
-                              const uint64_t* counts, const uint64_t* first) {
-  if (plan->rows < 2)
-    return fail(Status::InvalidArg, std::string(what) + ": the plan has " + std::to_string(plan->rows) +
-                                        " row: one parity row cannot tell which shard is wrong");
-  if (plan->k + plan->rows > 63)
-    return fail(Status::InvalidArg, std::string(what) + ": k + rows = " + std::to_string(plan->k + plan->rows) +
-                                        " exceeds 63 (a wave's tally keeps one slot per lane)");
-  if (!counts || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
-  return 0;
-}
-
 int slime_rs_plan_locate_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src, const uint32_t* cmp,
                                const uint64_t* filter, uint64_t* counts, uint64_t* first, void* stream) {
-  if (int rc = check_batch_plan("plan_locate_batch", plan, batch)) return rc;
-  if (int rc = check_locate_batch("plan_locate_batch", plan, src, cmp, counts, first)) return rc;
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  const RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), nullptr, filter, counts, first};
-  // A locate reads the plan's output table like any launch (slime_rs_plan_set_outputs).
-  plan->executed.store(true, std::memory_order_relaxed);
-  DeviceScope ds(plan->device);
-  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
-  return 0;
+  return locate_batch("plan_locate_batch", plan, batch, src, cmp, false, nullptr, filter, counts, first, stream);
 }
 
 int slime_rs_locate_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src, const uint8_t* cmp,
                                   const uint32_t* mapping, const uint64_t* filter, uint64_t* counts, uint64_t* first,
                                   void* stream) {
-  if (int rc = check_batch_plan("locate_objects_batch", plan, batch)) return rc;
-  if (int rc = check_locate_batch("locate_objects_batch", plan, src, cmp, counts, first)) return rc;
-  // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
-  if (!mapping) return fail(Status::InvalidArg, "locate_objects_batch: null mapping");
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  const RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(plan), mapping, filter, counts, first};
-  plan->executed.store(true, std::memory_order_relaxed);
-  DeviceScope ds(plan->device);
-  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
-  return 0;
-}
-
-// ---- plan-set locate (rs_locate_planset.hip) ----------------------------------------
-
-// What both plan-set locate forms check after check_batch_set, symbols or bytes, in this order.
-static int check_locate_set(const char* what, const slime_rs_planset* set, const void* src, const void* cmp,
-                            const uint64_t* counts, const uint64_t* first) {
-  if (set->max_rows < 2)
-    return fail(Status::InvalidArg, std::string(what) + ": no plan of the set has more than " +
-                                        std::to_string(set->max_rows) +
-                                        " row: one parity row cannot tell which shard is wrong");
-  if (set->k + set->max_rows > 63)
-    return fail(Status::InvalidArg, std::string(what) + ": k + max_rows = " + std::to_string(set->k + set->max_rows) +
-                                        " exceeds 63 (a wave's tally keeps one slot per lane)");
-  if (!counts || !first) return fail(Status::InvalidArg, std::string(what) + ": null result array");
-  if (!src || !cmp) return fail(Status::InvalidArg, std::string(what) + ": null buffer");
-  return 0;
+  return locate_batch("locate_objects_batch", plan, batch, src, cmp, true, mapping, filter, counts, first, stream);
 }
 
 int slime_rs_planset_locate_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src,
                                   const uint32_t* cmp, const uint64_t* filter, uint64_t* counts, uint64_t* first,
                                   void* stream) {
-  if (int rc = check_batch_set("planset_locate_batch", set, batch)) return rc;
-  if (int rc = check_locate_set("planset_locate_batch", set, src, cmp, counts, first)) return rc;
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), nullptr, filter, counts, first};
-  v.p.rows = set->max_rows;  // the result arrays' and the filter's row stride
-  DeviceScope ds(set->device);
-  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
-  return 0;
+  return locate_batch("planset_locate_batch", set, batch, src, cmp, false, nullptr, filter, counts, first, stream);
 }
 
 int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
                                           const uint8_t* cmp, const uint32_t* mapping, const uint64_t* filter,
                                           uint64_t* counts, uint64_t* first, void* stream) {
-  if (int rc = check_batch_set("planset_locate_objects_batch", set, batch)) return rc;
-  if (int rc = check_locate_set("planset_locate_objects_batch", set, src, cmp, counts, first)) return rc;
-  // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
-  if (!mapping) return fail(Status::InvalidArg, "planset_locate_objects_batch: null mapping");
-  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(set), mapping, filter, counts, first};
-  v.p.rows = set->max_rows;
-  DeviceScope ds(set->device);
-  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
-  return 0;
+  return locate_batch("planset_locate_objects_batch", set, batch, src, cmp, true, mapping, filter, counts, first,
+                      stream);
 }
 
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {
@@ -1254,7 +1240,7 @@ extern "C" int slime_rs_resolve_fallbacks(slime_rs_plan_t plan, uint8_t* slots, 
 static int encode_batch_launch(const char* what, slime_rs_plan* plan, const slime_rs_batch* batch, uint8_t* src,
                                uint8_t* dst, const uint64_t* sizes, uint32_t* mapping, uint32_t* status,
                                RaggedEncodeLaunch* a) {
-  if (int rc = check_batch_plan(what, plan, batch)) return rc;
+  if (int rc = check_batch(what, plan, batch)) return rc;
   if (!plan->in_seq)
     return fail(Status::InvalidArg, std::string(what) + ": the plan must read inputs 0..k-1 in that order "
                                                         "(slime_rs_plan_encode): padding depends on a chunk's position");

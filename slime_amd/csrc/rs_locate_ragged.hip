@@ -5,6 +5,21 @@
 // counts[o][slot] columns blamed on slot, first[o][slot] the lowest of them;
 // slots are the plan's k inputs, its rows, then `unlocated`.
 //
+// Plan sets (SET, one template): the same launch over a PLANNED batch, every
+// object classified with its own plan of a set -- slime_rs_planset_locate_batch
+// and slime_rs_planset_locate_objects_batch.  A degraded object is scrubbed
+// (rs_verify_ragged.hip, the SET forms) and located from its own survivor set:
+// its plan reads `k` present shards and checks the remaining present ones.
+// Results are nobj x (k + max_rows + 1): slot j < k is the object's plan's
+// input j, slot k + i (i < the plan's rows) its output row i, slots past the
+// plan's rows keep their initial values, and `unlocated` is slot k + max_rows
+// for every object.  Objects whose plan has one row report every mismatching
+// column as unlocated (locate_rule.hpp, set_slot).  What SET adds per object is
+// one plan record (two dependent scalar loads) and, for k <= 16, one 16-dword
+// line of input indices, taken when the walk enters the object; R -- the stored
+// rows a step carries -- is chosen from max_rows, and the filter is the nobj x
+// max_rows counts of a plan-set verify.
+//
 // Fast path -- verify's: the work comes from UnitWalk over the batch's unit
 // list (rs_ragged_walk.hpp), a tile goes in verify's steps (verify_step.hpp),
 // load_tile loads a step and dot4 computes its rows.  Instead of a tally per
@@ -27,7 +42,7 @@
 // (L % 4 columns an object) classify one column a lane and issue their own
 // atomics.
 //
-// Forms:
+// Forms (rs_locate_planset_*: the SET twins, the same bodies):
 //   k <= 16, 4-byte aligned src and cmp: rs_locate_ragged_kernel<K, W, R, ...>,
 //     four columns a lane, symbols and bytes from one body (BYTES).
 //   17 <= k (k + rows <= 63), or a base that is not 4-byte aligned:
@@ -47,14 +62,39 @@ namespace locate {
 
 template <int K, int W, int R, int UB, int C, bool BYTES>
 __global__ __launch_bounds__(kBlock) void rs_locate_ragged_kernel(SLIME_RLOCATE_PARAMS) {
-  locate_ragged_vectors<K, W, R, UB, C, BYTES>(SLIME_RLOCATE_PASS);
+  locate_vectors<K, W, R, UB, C, false, BYTES>(SLIME_RLOCATE_PASS);
 }
 
 template <bool BYTES>
 __global__ __launch_bounds__(kBlock) void rs_locate_ragged_column_kernel(SLIME_RLOCATE_PARAMS, uint32_t tile_cols,
                                                                          uint32_t unit_tiles) {
-  locate_ragged_columns<BYTES>(SLIME_RLOCATE_PASS, tile_cols, unit_tiles);
+  locate_columns<false, BYTES>(SLIME_RLOCATE_PASS, tile_cols, unit_tiles);
 }
+
+// The plan-set entry points: the shared bodies with the table as `coeff`, max_rows as `rows` and
+// no index arrays.
+#define SLIME_PLOCATE_PARAMS                                                                                      \
+  const uint8_t *__restrict__ in, const uint8_t *__restrict__ cmp, const Desc *__restrict__ descs,                \
+      const Unit *__restrict__ units, const Tail *__restrict__ tails, const uint32_t *__restrict__ table,         \
+      const uint32_t *__restrict__ mapping, const unsigned long long *__restrict__ filter,                        \
+      unsigned long long *__restrict__ counts, unsigned long long *__restrict__ first, uint32_t nunits,           \
+      uint64_t ntails, uint32_t max_rows, uint32_t k
+#define SLIME_PLOCATE_PASS \
+  in, cmp, descs, units, tails, table, nullptr, nullptr, mapping, filter, counts, first, nunits, ntails, max_rows, k
+
+template <int K, int W, int R, int UB, int C, bool BYTES>
+__global__ __launch_bounds__(kBlock) void rs_locate_planset_kernel(SLIME_PLOCATE_PARAMS) {
+  locate_vectors<K, W, R, UB, C, true, BYTES>(SLIME_PLOCATE_PASS);
+}
+
+template <bool BYTES>
+__global__ __launch_bounds__(kBlock) void rs_locate_planset_column_kernel(SLIME_PLOCATE_PARAMS, uint32_t tile_cols,
+                                                                          uint32_t unit_tiles) {
+  locate_columns<true, BYTES>(SLIME_PLOCATE_PASS, tile_cols, unit_tiles);
+}
+
+#undef SLIME_PLOCATE_PARAMS
+#undef SLIME_PLOCATE_PASS
 
 }  // namespace locate
 
@@ -62,43 +102,62 @@ namespace {
 
 using apply::kBlock;
 
+// One per kernel signature; (v).p.rows is the plan's rows or the set's max_rows.
 #define SLIME_RLOCATE_ARGS(v)                                                                                     \
   (const uint8_t*)(v).in, (const uint8_t*)(v).cmp, (v).w.desc, (v).w.units, (v).w.tails, (v).p.coeff,             \
       (v).p.in_idx, (v).p.out_idx, (v).mapping, (const unsigned long long*)(v).filter,                            \
       (unsigned long long*)(v).counts, (unsigned long long*)(v).first, (v).w.nunits, (v).w.ntails, (v).p.rows,    \
       (v).w.k
+#define SLIME_PLOCATE_ARGS(v)                                                                                     \
+  (const uint8_t*)(v).in, (const uint8_t*)(v).cmp, (v).w.desc, (v).w.units, (v).w.tails, (v).p.table,             \
+      (v).mapping, (const unsigned long long*)(v).filter, (unsigned long long*)(v).counts,                        \
+      (unsigned long long*)(v).first, (v).w.nunits, (v).w.ntails, (v).p.rows, (v).w.k
 
 constexpr uint64_t kLocateBlocks = 1024;  // four blocks a CU: the static walk hides latency by occupancy
 
-template <int K, int R, bool BYTES>
+template <int K, int R, bool SET, bool BYTES>
 hipError_t launch_vectors(const RaggedLocateLaunch& v, hipStream_t s) {
   constexpr int UB = ragged::unroll_for_k(K), C = ragged::unit_tiles_for_k(K), W = verify_step::width(K, R);
-  const uint64_t blocks = ragged::ragged_blocks(kLocateBlocks, v.w.nunits, v.w.ntails);
-  hipLaunchKernelGGL((locate::rs_locate_ragged_kernel<K, W, R, UB, C, BYTES>), dim3((uint32_t)blocks), dim3(kBlock), 0,
-                     s, SLIME_RLOCATE_ARGS(v));
+  const dim3 grid((uint32_t)ragged::ragged_blocks(kLocateBlocks, v.w.nunits, v.w.ntails));
+  if constexpr (SET)
+    hipLaunchKernelGGL((locate::rs_locate_planset_kernel<K, W, R, UB, C, BYTES>), grid, dim3(kBlock), 0, s,
+                       SLIME_PLOCATE_ARGS(v));
+  else
+    hipLaunchKernelGGL((locate::rs_locate_ragged_kernel<K, W, R, UB, C, BYTES>), grid, dim3(kBlock), 0, s,
+                       SLIME_RLOCATE_ARGS(v));
   return hipGetLastError();
 }
 
-template <int K>
+// R -- the stored rows a step carries -- from the plan's rows or the set's max_rows.
+template <int K, bool SET>
 hipError_t launch_rows(const RaggedLocateLaunch& v, hipStream_t s) {
   const bool bytes = v.mapping != nullptr;
   if (verify_step::stored_rows(v.p.rows) == 2)
-    return bytes ? launch_vectors<K, 2, true>(v, s) : launch_vectors<K, 2, false>(v, s);
-  return bytes ? launch_vectors<K, 4, true>(v, s) : launch_vectors<K, 4, false>(v, s);
+    return bytes ? launch_vectors<K, 2, SET, true>(v, s) : launch_vectors<K, 2, SET, false>(v, s);
+  return bytes ? launch_vectors<K, 4, SET, true>(v, s) : launch_vectors<K, 4, SET, false>(v, s);
 }
 
+template <bool SET, bool BYTES>
 hipError_t launch_columns(const RaggedLocateLaunch& v, hipStream_t s) {
-  const uint64_t blocks = ragged::ragged_blocks(kLocateBlocks, v.w.nunits, v.w.ntails);
-  if (v.mapping)
-    hipLaunchKernelGGL(locate::rs_locate_ragged_column_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
-                       SLIME_RLOCATE_ARGS(v), 256u * (uint32_t)v.w.U, (uint32_t)v.w.C);
+  const dim3 grid((uint32_t)ragged::ragged_blocks(kLocateBlocks, v.w.nunits, v.w.ntails));
+  const uint32_t tile_cols = 256u * (uint32_t)v.w.U, unit_tiles = (uint32_t)v.w.C;
+  if constexpr (SET)
+    hipLaunchKernelGGL(locate::rs_locate_planset_column_kernel<BYTES>, grid, dim3(kBlock), 0, s,
+                       SLIME_PLOCATE_ARGS(v), tile_cols, unit_tiles);
   else
-    hipLaunchKernelGGL(locate::rs_locate_ragged_column_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
-                       SLIME_RLOCATE_ARGS(v), 256u * (uint32_t)v.w.U, (uint32_t)v.w.C);
+    hipLaunchKernelGGL(locate::rs_locate_ragged_column_kernel<BYTES>, grid, dim3(kBlock), 0, s,
+                       SLIME_RLOCATE_ARGS(v), tile_cols, unit_tiles);
   return hipGetLastError();
 }
 
 #undef SLIME_RLOCATE_ARGS
+#undef SLIME_PLOCATE_ARGS
+
+template <bool SET>
+hipError_t launch_form(const RaggedLocateLaunch& v, bool vec, hipStream_t s) {
+  if (!vec) return v.mapping ? launch_columns<SET, true>(v, s) : launch_columns<SET, false>(v, s);
+  return ragged::with_k(v.w.k, [&](auto kc) { return launch_rows<decltype(kc)::value, SET>(v, s); });
+}
 
 }  // namespace
 
@@ -112,9 +171,7 @@ hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t s) {
   // The vector kernels are instantiated with the geometry of their K: the tables must be cut by it.
   if (vec && (v.w.U != ragged::unroll_for_k((int)v.w.k) || v.w.C != ragged::unit_tiles_for_k((int)v.w.k)))
     return hipErrorInvalidValue;
-  if (v.p.table) return launch_locate_planset(v, s);  // every object with its own plan of a set
-  if (!vec) return launch_columns(v, s);
-  return ragged::with_k(v.w.k, [&](auto kc) { return launch_rows<decltype(kc)::value>(v, s); });
+  return v.p.table ? launch_form<true>(v, vec, s) : launch_form<false>(v, vec, s);  // a set: a plan per object
 }
 
 }  // namespace slime

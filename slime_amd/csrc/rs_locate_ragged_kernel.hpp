@@ -1,11 +1,17 @@
 // Device side of the ragged locate (rs_locate_ragged.hip), symbols and stored
 // chunk bytes alike (BYTES: a stored word is big-endian and XOR-ed with its
-// object's mapping value, so every symbol is BE(word) ^ m): the filter's
-// verdict on an object, the fast path's per-lane mismatch flags, the rare
-// path's classification of one column by locate_rule.hpp, the fold of a wave's
-// classified columns into a Tally (lane = slot), the tail items and the
-// one-column-a-lane form.  rs_locate_ragged.hip's header comment describes the
-// scheme.
+// object's mapping value, so every symbol is BE(word) ^ m), one plan or a plan
+// set's table (SET): the filter's verdict on an object, the fast path's
+// per-lane mismatch flags, the rare path's classification of one column by
+// locate_rule.hpp, the fold of a wave's classified columns into a Tally (lane =
+// slot), the tail items and the one-column-a-lane form.  rs_locate_ragged.hip's
+// header comment describes the scheme.
+//
+// SET: `coeff` is the set's table (planset_table.hpp) and `rows` its max_rows,
+// in_idx / out_idx are null; when the walk enters an object its own plan -- k
+// input indices, coefficient rows, output indices, row count -- is read from
+// its record, and the column's slot goes through set_slot (locate_rule.hpp).
+// The helpers take the object's plan as their arguments either way.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,16 +25,20 @@ namespace locate {
 
 using apply::kBlock;
 using apply::kWaves;
+using apply::u32x16;
 using ragged::Desc;
 using ragged::ObjRef;
+using ragged::PlanRef;
+using ragged::PlanRows;
 using ragged::Tail;
 using ragged::Unit;
 using ragged::UnitWalk;
 using verify::be;
 using verify::Tally;
 
-// coeff / in_idx / out_idx / rows / k: the plan's; mapping: BYTES only; filter: NULL or nobj x rows
-// counts of a preceding verify; counts / first: nobj x (k + rows + 1).
+// coeff / in_idx / out_idx / rows / k: the plan's (SET: the table, null, null, max_rows); mapping:
+// BYTES only; filter: NULL or nobj x rows counts of a preceding verify; counts / first: nobj x
+// (k + rows + 1).
 #define SLIME_RLOCATE_PARAMS                                                                                      \
   const uint8_t *__restrict__ in, const uint8_t *__restrict__ cmp, const Desc *__restrict__ descs,                \
       const Unit *__restrict__ units, const Tail *__restrict__ tails, const uint32_t *__restrict__ coeff,         \
@@ -145,8 +155,9 @@ __device__ __forceinline__ uint32_t flag_tile(uint4 (&x)[U][K], uint4 (&s)[R][U]
 }
 
 // The tail items: one {object, column} per lane, classified and counted by the lane itself
-// (neighbouring lanes hold different objects: Tally's lane-per-slot scheme does not apply).
-template <bool BYTES>
+// (neighbouring lanes hold different objects: Tally's lane-per-slot scheme does not apply, and
+// with SET the lane reads its item's plan through its descriptor).
+template <bool SET, bool BYTES>
 __device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS) {
   const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint64_t nthr = (uint64_t)gridDim.x * kBlock;
@@ -155,10 +166,18 @@ __device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS) {
     const Tail it = tails[t];
     if (filtered_out(filter, it.obj, rows)) continue;
     const Desc* const d = descs + it.obj;
+    PlanRows pl{coeff, out_idx, rows};
+    const uint32_t* iidx = in_idx;
+    if constexpr (SET) {
+      const PlanRef p = ragged::read_plan(coeff, d);
+      pl = ragged::whole_plan(coeff, p);
+      iidx = coeff + p.in_off;
+    }
     uint32_t m = 0;
     if constexpr (BYTES) m = mapping[it.obj];
-    const uint32_t slot = classify_column<BYTES>(in + (d->src_off << 2), cmp + (d->dst_off << 2), coeff, in_idx,
-                                                 d->src_shard << 2, out_idx, d->dst_shard << 2, rows, k, m, it.col);
+    uint32_t slot = classify_column<BYTES>(in + (d->src_off << 2), cmp + (d->dst_off << 2), pl.coeff, iidx,
+                                           d->src_shard << 2, pl.oidx, d->dst_shard << 2, pl.rows, k, m, it.col);
+    if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
     if (slot != kNoSlot) {
       atomicAdd(counts + (uint64_t)it.obj * nslots + slot, 1ull);
       atomicMin(first + (uint64_t)it.obj * nslots + slot, (unsigned long long)it.col);
@@ -167,9 +186,10 @@ __device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS) {
 }
 
 // Four columns a lane, k = K <= 16 over 4-byte aligned bases: a static walk over the unit list,
-// a tile in verify's steps of W vectors a lane, one step at a time.
-template <int K, int W, int R, int UB, int C, bool BYTES>
-__device__ __forceinline__ void locate_ragged_vectors(SLIME_RLOCATE_PARAMS) {
+// a tile in verify's steps of W vectors a lane, one step at a time.  With SET, R comes from the
+// set's max_rows; row_bases and flag_tile clip to the object's own rows.
+template <int K, int W, int R, int UB, int C, bool SET, bool BYTES>
+__device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS) {
   static_assert(K > 0 && K <= 16 && W >= 1 && W <= UB && W <= 4, "compile-time k; a step is at most a tile");
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -186,19 +206,38 @@ __device__ __forceinline__ void locate_ragged_vectors(SLIME_RLOCATE_PARAMS) {
   const uint8_t* cb = cmp;
   uint64_t ishard = 0, cshard = 0;
   uint32_t m = 0;
+  // The current object's plan and its input indices: the launch's, or with SET placeholders inside
+  // the table until the walk enters an object.
+  PlanRows pl{coeff, SET ? coeff : out_idx, SET ? 1 : rows};
+  const uint32_t* iidx = SET ? coeff : in_idx;
   bool skip = false;
   while (w.live) {
     if (w.fresh) {  // the first tile since the object changed
       skip = filtered_out(filter, w.obj, rows);
       if (!skip) {
-        if constexpr (BYTES) m = mapping[w.obj];  // wave-uniform
-        ib = in + (w.d.src_off << 2);
-        ishard = w.d.src_shard << 2;
+        // Two branches with the same three source-side statements: with SET the index line is read
+        // before them.  The statement order is what the kernels' machine code is compared by
+        // (tools/kernel_ids.py); a shared tail behind the read changes both families' kernels.
+        if constexpr (SET) {
+          const PlanRef p = ragged::load_plan(coeff, descs, w.obj);
+          pl = ragged::whole_plan(coeff, p);
+          iidx = coeff + p.in_off;
+          const u32x16 idx = *reinterpret_cast<const u32x16*>(iidx);  // K <= 16: one line
+          if constexpr (BYTES) m = mapping[w.obj];  // wave-uniform
+          ib = in + (w.d.src_off << 2);
+          ishard = w.d.src_shard << 2;
 #pragma unroll
-        for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)in_idx[j] * ishard;
+          for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)idx[j] * ishard;
+        } else {
+          if constexpr (BYTES) m = mapping[w.obj];  // wave-uniform
+          ib = in + (w.d.src_off << 2);
+          ishard = w.d.src_shard << 2;
+#pragma unroll
+          for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)in_idx[j] * ishard;
+        }
         cb = cmp + (w.d.dst_off << 2);
         cshard = w.d.dst_shard << 2;
-        verify::row_bases<R>(rb, cb, out_idx, cshard, 0, rows);
+        verify::row_bases<R>(rb, cb, pl.oidx, cshard, 0, pl.rows);
         unsigned long long* const res = counts + (uint64_t)w.obj * nslots;
         if (res != t.mism) {
           t.flush();
@@ -212,7 +251,8 @@ __device__ __forceinline__ void locate_ragged_vectors(SLIME_RLOCATE_PARAMS) {
       for (uint32_t tb = t0; tb < tend; tb += 64 * W) {
         uint4 x[W][K], s[R][W];
         verify::load_tile<K, W, R, uint32_t>(x, s, sb, rb, tb + lane, tend);
-        const uint32_t bits = flag_tile<K, W, R, BYTES, uint32_t>(x, s, cb, coeff, out_idx, cshard, rows, m, tb, tend, lane);
+        const uint32_t bits =
+            flag_tile<K, W, R, BYTES, uint32_t>(x, s, cb, pl.coeff, pl.oidx, cshard, pl.rows, m, tb, tend, lane);
         if (__ballot(bits != 0)) {
           // Rare path: word q & 3 of unit q >> 2, every lane that flagged it; for one q the lanes
           // are in column order.
@@ -221,7 +261,10 @@ __device__ __forceinline__ void locate_ragged_vectors(SLIME_RLOCATE_PARAMS) {
             if (!__ballot(hit)) continue;
             const uint64_t col = ((uint64_t)(tb + 64 * (q >> 2) + lane) << 2) + (q & 3u);
             uint32_t slot = kNoSlot;
-            if (hit) slot = classify_column<BYTES>(ib, cb, coeff, in_idx, ishard, out_idx, cshard, rows, k, m, col);
+            if (hit) {
+              slot = classify_column<BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col);
+              if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
+            }
             tally_slots(t, slot, col);
           }
         }
@@ -230,13 +273,14 @@ __device__ __forceinline__ void locate_ragged_vectors(SLIME_RLOCATE_PARAMS) {
     w.advance();
   }
   t.flush();
-  locate_tails<BYTES>(SLIME_RLOCATE_PASS);
+  locate_tails<SET, BYTES>(SLIME_RLOCATE_PASS);
 }
 
 // One column a lane over the same unit list (static walk): generic k through wide_dot, any
-// alignment.  tile_cols = 256 UB, unit_tiles = C of the batch's geometry.
-template <bool BYTES>
-__device__ __forceinline__ void locate_ragged_columns(SLIME_RLOCATE_PARAMS, uint32_t tile_cols, uint32_t unit_tiles) {
+// alignment; with SET the unit's object's plan is read per unit.  tile_cols = 256 UB,
+// unit_tiles = C of the batch's geometry.
+template <bool SET, bool BYTES>
+__device__ __forceinline__ void locate_columns(SLIME_RLOCATE_PARAMS, uint32_t tile_cols, uint32_t unit_tiles) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t nwaves = gridDim.x * kWaves;
@@ -246,6 +290,13 @@ __device__ __forceinline__ void locate_ragged_columns(SLIME_RLOCATE_PARAMS, uint
     const Unit u = units[e];
     if (filtered_out(filter, u.obj, rows)) continue;
     const ObjRef d = ragged::load_desc(descs, u.obj);
+    PlanRows pl{coeff, out_idx, rows};
+    const uint32_t* iidx = in_idx;
+    if constexpr (SET) {
+      const PlanRef p = ragged::load_plan(coeff, descs, u.obj);
+      pl = ragged::whole_plan(coeff, p);
+      iidx = coeff + p.in_off;
+    }
     uint32_t m = 0;
     if constexpr (BYTES) m = mapping[u.obj];
     const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
@@ -264,25 +315,28 @@ __device__ __forceinline__ void locate_ragged_columns(SLIME_RLOCATE_PARAMS, uint
       const bool ok = bw + lane < b1;
       const uint64_t col = ok ? bw + lane : bw;
       auto in_word = [&](uint32_t j) {
-        const uint32_t v = *reinterpret_cast<const uint32_t*>(ib + (uint64_t)in_idx[j] * ishard + (col << 2));
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(ib + (uint64_t)iidx[j] * ishard + (col << 2));
         return BYTES ? be(v) ^ m : v;
       };
       bool bad = false;
-      for (uint32_t i = 0; i < rows; ++i) {
-        const uint32_t r = apply::wide_dot(coeff + (uint64_t)i * cs, k, in_word);
-        const uint32_t stored = *reinterpret_cast<const uint32_t*>(cb + (uint64_t)out_idx[i] * cshard + (col << 2));
+      for (uint32_t i = 0; i < pl.rows; ++i) {
+        const uint32_t r = apply::wide_dot(pl.coeff + (uint64_t)i * cs, k, in_word);
+        const uint32_t stored = *reinterpret_cast<const uint32_t*>(cb + (uint64_t)pl.oidx[i] * cshard + (col << 2));
         bad |= stored != (BYTES ? be(r ^ m) : r);
       }
       bad &= ok;
       if (__ballot(bad)) {
         uint32_t slot = kNoSlot;
-        if (bad) slot = classify_column<BYTES>(ib, cb, coeff, in_idx, ishard, out_idx, cshard, rows, k, m, col);
+        if (bad) {
+          slot = classify_column<BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col);
+          if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
+        }
         tally_slots(t, slot, col);
       }
     }
   }
   t.flush();
-  locate_tails<BYTES>(SLIME_RLOCATE_PASS);
+  locate_tails<SET, BYTES>(SLIME_RLOCATE_PASS);
 }
 
 }  // namespace locate

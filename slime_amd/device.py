@@ -265,16 +265,7 @@ class Plan:
         """One launch over a ragged batch (slime_rs_plan_execute_batch): every span of `batch`, each
         with its own offsets, strides and length; offsets are in uint32 elements from the tensors'
         starts.  dst may be src (outputs in each object's own slots).  Asynchronous."""
-        for t in (src, dst):
-            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
-            if _dev_index(t) != self.device:
-                raise ValueError("tensor is not on the plan's device")
-        if batch.device != self.device or batch.k != self.k:
-            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
-                             f"the plan has k={self.k} on device {self.device}")
-        batch._check_extent(src, src_offset, 0, self.in_max)
-        batch._check_extent(dst, dst_offset, 1, self.rows - 1 if self.out_max is None else self.out_max)
+        _check_symbols_batch(self, src, dst, batch, src_offset, dst_offset)
         _note_unprobed(src)
         if dst.data_ptr() != src.data_ptr():
             _note_unprobed(dst)
@@ -291,16 +282,7 @@ class Plan:
         (batch.nobj, rows), first a column inside the object or -1.  Objects with L == 0 and
         N.NO_PLAN objects of a planned batch keep (0, -1).  Asynchronous; nothing but the two
         results is written."""
-        for t in (src, cmp):
-            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
-            if _dev_index(t) != self.device:
-                raise ValueError("tensor is not on the plan's device")
-        if batch.device != self.device or batch.k != self.k:
-            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
-                             f"the plan has k={self.k} on device {self.device}")
-        batch._check_extent(src, src_offset, 0, self.in_max)
-        batch._check_extent(cmp, cmp_offset, 1, self.rows - 1 if self.out_max is None else self.out_max)
+        _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
         mism, first = _verify_results(batch.nobj, self.rows, self.device)
         if batch.nobj == 0:
             return mism, first  # no results: nothing to initialise, nothing to launch
@@ -321,16 +303,7 @@ class Plan:
         the mismatches tensor of a preceding verify_batch of this plan and batch on the same
         stream -- objects it shows clean are passed over on the device and keep (0, -1).  Needs
         rows >= 2 and k + rows <= 63.  Asynchronous; nothing but the two results is written."""
-        for t in (src, cmp):
-            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
-            if _dev_index(t) != self.device:
-                raise ValueError("tensor is not on the plan's device")
-        if batch.device != self.device or batch.k != self.k:
-            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
-                             f"the plan has k={self.k} on device {self.device}")
-        batch._check_extent(src, src_offset, 0, self.in_max)
-        batch._check_extent(cmp, cmp_offset, 1, self.rows - 1 if self.out_max is None else self.out_max)
+        _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
         _check_locate_filter(filter, batch.nobj, self.rows, self.device)
         counts, first = _verify_results(batch.nobj, self.k + self.rows + 1, self.device)
         if batch.nobj == 0:
@@ -511,19 +484,7 @@ class PlanSet:
                       stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0, dst_offset: int = 0) -> None:
         """One launch over a planned batch (slime_rs_planset_execute_batch): every object with its
         own plan of the set.  dst may be src (each object repaired in its own slots).  Asynchronous."""
-        for t in (src, dst):
-            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
-            if _dev_index(t) != self.device:
-                raise ValueError("tensor is not on the plan set's device")
-        if getattr(batch, "plans", None) is None:
-            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
-        if batch.device != self.device or batch.k != self.k or batch.nplans != self.nplans:
-            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
-                             f"the set has {self.nplans} plans of k={self.k} on device {self.device}")
-        # The set-wide highest shard indices: every object is checked as if it ran the widest plan.
-        batch._check_extent(src, src_offset, 0, self.in_max)
-        batch._check_extent(dst, dst_offset, 1, self.out_max)
+        _check_symbols_batch(self, src, dst, batch, src_offset, dst_offset)
         _note_unprobed(src)
         if dst.data_ptr() != src.data_ptr():
             _note_unprobed(dst)
@@ -539,19 +500,7 @@ class PlanSet:
         a different survivor set each.  Returns (mismatches, first) of shape
         (batch.nobj, max_rows); rows at or past an object's own plan's row count, and N.NO_PLAN
         objects, keep (0, -1).  Asynchronous; nothing but the two results is written."""
-        for t in (src, cmp):
-            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
-            if _dev_index(t) != self.device:
-                raise ValueError("tensor is not on the plan set's device")
-        if getattr(batch, "plans", None) is None:
-            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
-        if batch.device != self.device or batch.k != self.k or batch.nplans != self.nplans:
-            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
-                             f"the set has {self.nplans} plans of k={self.k} on device {self.device}")
-        # The set-wide highest shard indices: every object is checked as if it ran the widest plan.
-        batch._check_extent(src, src_offset, 0, self.in_max)
-        batch._check_extent(cmp, cmp_offset, 1, self.out_max)
+        _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
         mism, first = _verify_results(batch.nobj, self.max_rows, self.device)
         if batch.nobj == 0:
             return mism, first
@@ -609,19 +558,7 @@ class PlanSet:
         or the mismatches tensor of a preceding PlanSet.verify_batch of this set and batch on the
         same stream.  Needs max_rows >= 2 and k + max_rows <= 63.  Asynchronous; nothing but the
         two results is written."""
-        for t in (src, cmp):
-            if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-                raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
-            if _dev_index(t) != self.device:
-                raise ValueError("tensor is not on the plan set's device")
-        if getattr(batch, "plans", None) is None:
-            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
-        if batch.device != self.device or batch.k != self.k or batch.nplans != self.nplans:
-            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
-                             f"the set has {self.nplans} plans of k={self.k} on device {self.device}")
-        # The set-wide highest shard indices: every object is checked as if it ran the widest plan.
-        batch._check_extent(src, src_offset, 0, self.in_max)
-        batch._check_extent(cmp, cmp_offset, 1, self.out_max)
+        _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
         _check_locate_filter(filter, batch.nobj, self.max_rows, self.device)
         counts, first = _verify_results(batch.nobj, self.k + self.max_rows + 1, self.device)
         if batch.nobj == 0:
@@ -844,6 +781,38 @@ def verify_objects(plan: Plan, slots: torch.Tensor, slot_stride: int, L: int, no
 
 # ---- ragged byte objects: stored chunks of objects of different lengths in one launch ----
 
+def _check_batch_plan(plan_or_set, batch: "Batch") -> int:
+    """ValueError unless `batch` was made for plan_or_set's k and device (a PlanSet: a planned batch
+    of its plan count).  Returns the highest output shard index the extent checks must allow."""
+    dev = plan_or_set.device
+    if isinstance(plan_or_set, PlanSet):
+        if getattr(batch, "plans", None) is None:
+            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
+        if batch.device != dev or batch.k != plan_or_set.k or batch.nplans != plan_or_set.nplans:
+            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
+                             f"the set has {plan_or_set.nplans} plans of k={plan_or_set.k} on device {dev}")
+        return plan_or_set.out_max  # set-wide: every object is checked as if it ran the widest plan
+    if batch.device != dev or batch.k != plan_or_set.k:
+        raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
+                         f"the plan has k={plan_or_set.k} on device {dev}")
+    return plan_or_set.rows - 1 if plan_or_set.out_max is None else plan_or_set.out_max
+
+
+def _check_symbols_batch(plan_or_set, a: torch.Tensor, b: torch.Tensor, batch: "Batch", a_offset: int,
+                         b_offset: int) -> None:
+    """The host-side checks of execute_batch, verify_batch and locate_batch of a Plan or a PlanSet,
+    all before any C call: the symbol-side sibling of _check_objects_batch."""
+    whose = "plan set's" if isinstance(plan_or_set, PlanSet) else "plan's"
+    for t in (a, b):
+        if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+            raise TypeError("plan buffers must be contiguous int32/uint32 tensors")
+        if _dev_index(t) != plan_or_set.device:
+            raise ValueError(f"tensor is not on the {whose} device")
+    out_max = _check_batch_plan(plan_or_set, batch)
+    batch._check_extent(a, a_offset, 0, plan_or_set.in_max)
+    batch._check_extent(b, b_offset, 1, out_max)
+
+
 def _check_objects_batch(what: str, plan_or_set, a: torch.Tensor, b: torch.Tensor, batch: "Batch",
                          mapping: torch.Tensor) -> bool:
     """The host-side checks of the two byte launches, all ValueError and all before any C call.
@@ -857,18 +826,7 @@ def _check_objects_batch(what: str, plan_or_set, a: torch.Tensor, b: torch.Tenso
             raise ValueError(f"{what}: chunk buffers must be contiguous uint8 tensors")
         if _dev_index(t) != dev:
             raise ValueError(f"{what}: tensor is not on the plan's device")
-    if is_set:
-        if getattr(batch, "plans", None) is None:
-            raise ValueError("the batch carries no plan indices: create it with Batch(..., plans=..., nplans=...)")
-        if batch.device != dev or batch.k != plan_or_set.k or batch.nplans != plan_or_set.nplans:
-            raise ValueError(f"the batch is for {batch.nplans} plans of k={batch.k} on device {batch.device}, "
-                             f"the set has {plan_or_set.nplans} plans of k={plan_or_set.k} on device {dev}")
-        out_max = plan_or_set.out_max  # set-wide: every object is checked as if it ran the widest plan
-    else:
-        if batch.device != dev or batch.k != plan_or_set.k:
-            raise ValueError(f"the batch is for k={batch.k} on device {batch.device}, "
-                             f"the plan has k={plan_or_set.k} on device {dev}")
-        out_max = plan_or_set.rows - 1 if plan_or_set.out_max is None else plan_or_set.out_max
+    out_max = _check_batch_plan(plan_or_set, batch)
     # A span's offsets and strides count 4-byte words of chunk bytes.
     batch._check_extent(a, 0, 0, plan_or_set.in_max, unit=4)
     batch._check_extent(b, 0, 1, out_max, unit=4)
