@@ -1,5 +1,6 @@
 // The locate rule (slime_amd/csrc/locate_rule.hpp) on the CPU, over the product's
-// parity matrices (rs_matrix.cpp) of 3/5, 4/6, 8/12, 10/14, 17/20 and 33/50 and a
+// parity matrices (rs_matrix.cpp) of 3/5, 4/6, 8/12, 10/14, 17/20, 33/50, 61/63 and
+// 3/63 (the last two use all 63 slots: k = 61 with 2 rows, k = 3 with 60) and a
 // matrix with zero entries:
 //   every single-shard error in every slot, delta in {1, 4, p-1, 2^31}, random
 //   deltas, and stored parity t + p for t < 5, is named;
@@ -214,7 +215,8 @@ void run(const Code& code, uint64_t seed, bool mds) {
 
 int main(int argc, char** argv) {
   print_cases = argc > 1 && !strcmp(argv[1], "--cases");
-  const int codes[][2] = {{3, 5}, {4, 6}, {8, 12}, {10, 14}, {17, 20}, {33, 50}};
+  // 61/63 and 3/63 fill all 63 slots: `cand` starts with bits above 32 set, and 60 rows feed it.
+  const int codes[][2] = {{3, 5}, {4, 6}, {8, 12}, {10, 14}, {17, 20}, {33, 50}, {61, 63}, {3, 63}};
   for (const auto& c : codes) run(parity_code(c[0], c[1]), 1000 * c[0] + c[1], true);
   // A matrix with zero entries: a zero in row 0, a zero below it, an input that reaches one row
   // only, one that reaches none, and two proportional columns.

@@ -26,7 +26,7 @@ def binary():
 
 
 def test_locate_rule(binary):
-    """Every single-shard error in every slot of 3/5 ... 33/50 and of a matrix with zeros is named,
+    """Every single-shard error in every slot of 3/5 ... 33/50, 61/63, 3/63 and of a matrix with zeros is named,
     aliases classify as the rule says, and 10^5 random syndromes and double errors per matrix
     agree with the brute-force restatement."""
     r = subprocess.run([binary], capture_output=True, text=True, timeout=300)
@@ -64,6 +64,11 @@ def test_python_reference_equals_the_cpp_rule(binary):
         assert R.slots_of_object(coeff, ins, st)[0] == slot, (k, rows, x, stored)
         seen.add("clean" if slot == R.CLEAN else "input" if slot < k else "row" if slot < k + rows else "unlocated")
     assert seen == {"clean", "input", "row", "unlocated"}
+    # the two codes that fill all 63 slots: every input of k = 61 (bits of `cand` above 32) and
+    # every one of 60 rows is named at least once, and both say unlocated at slot 63
+    for k, rows in ((61, 2), (3, 60)):
+        named = {slot for coeff, _, _, slot in cases if coeff.shape == (rows, k)}
+        assert named == set(range(64)) | {R.CLEAN}, (k, rows, sorted(set(range(64)) - named))
 
 
 def test_reference_tally():
