@@ -561,6 +561,53 @@ int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch
                                           const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
                                           uint64_t *counts, uint64_t *first, void *stream);
 
+/* ---- pair locate: name TWO wrong shards per column ------------------------------
+ * The four locate calls above with a pair rule behind their rule, for plans of
+ * rows >= 4 (8/12, 10/14, 16/20, scrub plans of four rows or more): four
+ * syndromes decide two errors as two decide one.  Two whole chunks of an object
+ * wrong -- truncated, zeroed, stale -- makes every column of the object
+ * unlocated for the calls above; these name both shards on the device.
+ * With h_a the column of slot a -- (c[0][a], ..., c[rows-1][a]) for an input
+ * a < k, the unit vector e_i for output row slot k + i -- a column is classified
+ * in this order:
+ *   1. the rule above names a slot or says clean: that is the answer;
+ *   2. rows < 4: unlocated, as above;
+ *   3. exactly two d_i set: those two output rows (bit-wise, as d_i is);
+ *   4. P = the unordered pairs {a, b} of slots with h_a, h_b independent and
+ *      s = alpha*h_a + beta*h_b for some alpha != 0, beta != 0.  |P| == 1: both
+ *      slots are named.  Anything else: unlocated.
+ * For the plans this library builds (the MDS code restricted to the shards a
+ * plan touches: distance rows + 1 >= 5) one or two wrong shards in a column are
+ * always named.  Three or more in one column are unlocated, or blamed on a
+ * wrong pair with probability about (k + rows)^2 / (2 p^(rows - 2)) per such
+ * column.  For slime_rs_plan_matrix plans the rule is applied as written,
+ * whatever the matrix.
+ * Results have the shape, initialisation and meaning of the calls above.  A
+ * column decided as a pair adds 1 to counts of BOTH slots and takes part in
+ * first of both; `unlocated` stays the last slot.  Arguments, addressing, the
+ * filter and the forms are those of each call's twin above.  Sets: an object
+ * whose own plan has rows_o >= 4 gets the pair rule, 2 <= rows_o < 4 the rule
+ * above, rows_o < 2 reports every mismatching column as unlocated.
+ * Asynchronous, no scratch (a block keeps the flagged columns' syndromes in
+ * rows x 256 words of LDS, at most 60 KiB), a static walk, no counter set,
+ * capturable; the plan is marked launched.  SLIME_RS_ERR_INVALID_ARG, in this
+ * order: the twin's handle and batch checks; rows < 4 (a set: max_rows < 4);
+ * k + rows > 63; null result arrays; null buffers; for the byte forms a null
+ * mapping.  Out of scope: three or more wrong shards per column, correcting in
+ * place, matrix-core forms, k + rows > 63, device digests. */
+int slime_rs_plan_locate_pairs_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
+                                     const uint32_t *cmp, const uint64_t *filter, uint64_t *counts, uint64_t *first,
+                                     void *stream);
+int slime_rs_locate_pairs_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t *src,
+                                        const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
+                                        uint64_t *counts, uint64_t *first, void *stream);
+int slime_rs_planset_locate_pairs_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t *src,
+                                        const uint32_t *cmp, const uint64_t *filter, uint64_t *counts,
+                                        uint64_t *first, void *stream);
+int slime_rs_planset_locate_pairs_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
+                                                const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
+                                                uint64_t *counts, uint64_t *first, void *stream);
+
 /* ---- ragged byte encode: ingest objects of different sizes in one launch -------
  * slime_rs_encode_objects over the spans of a batch, each object with its own
  * size: the write side of the four launches above.  The batch

@@ -741,8 +741,13 @@ int verify_objects_batch(const char* what, H* h, slime_rs_batch* batch, const ui
 }
 
 // What the locate forms check after check_batch, symbols or bytes, in this order; rows: result_rows.
-int check_locate_batch(const char* what, bool set, uint32_t k, uint32_t rows, const void* src, const void* cmp,
-                       const uint64_t* counts, const uint64_t* first) {
+int check_locate_batch(const char* what, bool set, bool pairs, uint32_t k, uint32_t rows, const void* src,
+                       const void* cmp, const uint64_t* counts, const uint64_t* first) {
+  if (pairs && rows < 4)
+    return fail(Status::InvalidArg, std::string(what) +
+                                        (set ? ": no plan of the set has more than " : ": the plan has ") +
+                                        std::to_string(rows) + (rows == 1 ? " row" : " rows") +
+                                        ": two wrong shards in a column take four rows to name");
   if (rows < 2)
     return fail(Status::InvalidArg, std::string(what) +
                                         (set ? ": no plan of the set has more than " : ": the plan has ") +
@@ -756,13 +761,15 @@ int check_locate_batch(const char* what, bool set, uint32_t k, uint32_t rows, co
   return 0;
 }
 
-// Ragged locate (rs_locate_ragged.hip), symbols (bytes = false, no mapping) or stored chunk bytes.
+// Ragged locate (rs_locate_ragged.hip), symbols (bytes = false, no mapping) or stored chunk bytes;
+// pairs: the pair rule behind it (rs_locate_pairs_ragged.hip).
 template <class H>
 int locate_batch(const char* what, H* h, slime_rs_batch* batch, const void* src, const void* cmp, bool bytes,
-                 const uint32_t* mapping, const uint64_t* filter, uint64_t* counts, uint64_t* first, void* stream) {
+                 const uint32_t* mapping, const uint64_t* filter, uint64_t* counts, uint64_t* first, void* stream,
+                 bool pairs = false) {
   if (int rc = check_batch(what, h, batch)) return rc;
-  if (int rc = check_locate_batch(what, std::is_same<H, slime_rs_planset>::value, h->k, result_rows(h), src, cmp,
-                                  counts, first))
+  if (int rc = check_locate_batch(what, std::is_same<H, slime_rs_planset>::value, pairs, h->k, result_rows(h), src,
+                                  cmp, counts, first))
     return rc;
   // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
   if (bytes && !mapping) return fail(Status::InvalidArg, std::string(what) + ": null mapping");
@@ -771,7 +778,7 @@ int locate_batch(const char* what, H* h, slime_rs_batch* batch, const void* src,
   v.p.rows = result_rows(h);  // the result arrays' and the filter's row stride
   mark_launched(h);
   DeviceScope ds(h->device);
-  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
+  HIP_TRY(pairs ? launch_locate_pairs_ragged(v, (hipStream_t)stream) : launch_locate_ragged(v, (hipStream_t)stream));
   return 0;
 }
 
@@ -940,6 +947,36 @@ int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch
                                           uint64_t* counts, uint64_t* first, void* stream) {
   return locate_batch("planset_locate_objects_batch", set, batch, src, cmp, true, mapping, filter, counts, first,
                       stream);
+}
+
+// ---- pair locate (rs_locate_pairs_ragged.hip) ---------------------------------------
+
+int slime_rs_plan_locate_pairs_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src,
+                                     const uint32_t* cmp, const uint64_t* filter, uint64_t* counts, uint64_t* first,
+                                     void* stream) {
+  return locate_batch("plan_locate_pairs_batch", plan, batch, src, cmp, false, nullptr, filter, counts, first, stream,
+                      true);
+}
+
+int slime_rs_locate_pairs_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint8_t* src,
+                                        const uint8_t* cmp, const uint32_t* mapping, const uint64_t* filter,
+                                        uint64_t* counts, uint64_t* first, void* stream) {
+  return locate_batch("locate_pairs_objects_batch", plan, batch, src, cmp, true, mapping, filter, counts, first,
+                      stream, true);
+}
+
+int slime_rs_planset_locate_pairs_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint32_t* src,
+                                        const uint32_t* cmp, const uint64_t* filter, uint64_t* counts,
+                                        uint64_t* first, void* stream) {
+  return locate_batch("planset_locate_pairs_batch", set, batch, src, cmp, false, nullptr, filter, counts, first,
+                      stream, true);
+}
+
+int slime_rs_planset_locate_pairs_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t* src,
+                                                const uint8_t* cmp, const uint32_t* mapping, const uint64_t* filter,
+                                                uint64_t* counts, uint64_t* first, void* stream) {
+  return locate_batch("planset_locate_pairs_objects_batch", set, batch, src, cmp, true, mapping, filter, counts,
+                      first, stream, true);
 }
 
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {

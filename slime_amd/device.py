@@ -294,7 +294,7 @@ class Plan:
 
     def locate_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: "Batch", filter: Optional[torch.Tensor] = None,
                      stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
-                     cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+                     cmp_offset: int = 0, max_wrong: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
         """Name the wrong shards of a ragged batch in one launch (slime_rs_plan_locate_batch):
         addressing as verify_batch.  Returns (counts, first): int64 tensors of shape
         (batch.nobj, k + rows + 1); counts[o, s] is the number of columns of object o blamed on
@@ -302,17 +302,21 @@ class Plan:
         output rows (locate_slots() gives their shard indices), then `unlocated`.  filter: None, or
         the mismatches tensor of a preceding verify_batch of this plan and batch on the same
         stream -- objects it shows clean are passed over on the device and keep (0, -1).  Needs
-        rows >= 2 and k + rows <= 63.  Asynchronous; nothing but the two results is written."""
+        rows >= 2 and k + rows <= 63.  Asynchronous; nothing but the two results is written.
+        max_wrong=2 (slime_rs_plan_locate_pairs_batch, rows >= 4): a column with two wrong shards
+        is named too -- it counts for both of its slots and takes part in `first` of both."""
+        pairs = _check_max_wrong(max_wrong)
         _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
         _check_locate_filter(filter, batch.nobj, self.rows, self.device)
         counts, first = _verify_results(batch.nobj, self.k + self.rows + 1, self.device)
         if batch.nobj == 0:
             return counts, first  # no results: nothing to initialise, nothing to launch
-        N.check(lib.slime_rs_plan_locate_batch(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
-                                               ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
-                                               ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
-                                               ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
-                                               _stream_handle(self.device, stream)))
+        call = lib.slime_rs_plan_locate_pairs_batch if pairs else lib.slime_rs_plan_locate_batch
+        N.check(call(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                     ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+                     ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                     ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                     _stream_handle(self.device, stream)))
         return counts, first
 
     def locate_slots(self) -> list[int]:
@@ -548,7 +552,7 @@ class PlanSet:
 
     def locate_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, filter: Optional[torch.Tensor] = None,
                      stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
-                     cmp_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+                     cmp_offset: int = 0, max_wrong: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
         """Plan.locate_batch with every object classified by its own plan of the set
         (slime_rs_planset_locate_batch): a degraded object is located from its own survivor set.
         Returns (counts, first) of shape (batch.nobj, k + max_rows + 1): for object o, slot j < k is
@@ -557,19 +561,21 @@ class PlanSet:
         object whose plan has one row reports every mismatching column as unlocated.  filter: None,
         or the mismatches tensor of a preceding PlanSet.verify_batch of this set and batch on the
         same stream.  Needs max_rows >= 2 and k + max_rows <= 63.  Asynchronous; nothing but the
-        two results is written."""
+        two results is written.  max_wrong=2 (slime_rs_planset_locate_pairs_batch, max_rows >= 4):
+        objects whose own plan has four rows or more have columns with two wrong shards named too,
+        the others are classified as with max_wrong=1."""
+        pairs = _check_max_wrong(max_wrong)
         _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
         _check_locate_filter(filter, batch.nobj, self.max_rows, self.device)
         counts, first = _verify_results(batch.nobj, self.k + self.max_rows + 1, self.device)
         if batch.nobj == 0:
             return counts, first  # no results: nothing to initialise, nothing to launch
-        N.check(lib.slime_rs_planset_locate_batch(self._h, batch._h,
-                                                  ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
-                                                  ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
-                                                  ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
-                                                  ctypes.c_void_p(counts.data_ptr()),
-                                                  ctypes.c_void_p(first.data_ptr()),
-                                                  _stream_handle(self.device, stream)))
+        call = lib.slime_rs_planset_locate_pairs_batch if pairs else lib.slime_rs_planset_locate_batch
+        N.check(call(self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+                     ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+                     ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                     ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                     _stream_handle(self.device, stream)))
         return counts, first
 
     def locate_slots(self, i: int) -> list:
@@ -598,6 +604,13 @@ def _verify_results(nobj: int, rows: int, device: int) -> tuple[torch.Tensor, to
     shape = (nobj, rows)
     return (torch.empty(shape, dtype=torch.int64, device=f"cuda:{device}"),
             torch.empty(shape, dtype=torch.int64, device=f"cuda:{device}"))
+
+
+def _check_max_wrong(max_wrong: int) -> bool:
+    """locate's max_wrong keyword: 1, or 2 for the pair calls.  Returns whether it is 2."""
+    if max_wrong not in (1, 2) or isinstance(max_wrong, bool):
+        raise ValueError(f"max_wrong must be 1 or 2 (wrong shards named per column), not {max_wrong!r}")
+    return max_wrong == 2
 
 
 def _check_locate_filter(filter: Optional[torch.Tensor], nobj: int, rows: int, device: int) -> None:
@@ -874,21 +887,27 @@ def verify_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batc
 
 
 def locate_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, mapping: torch.Tensor,
-                         filter: Optional[torch.Tensor] = None,
-                         stream: Optional[torch.cuda.Stream] = None) -> tuple[torch.Tensor, torch.Tensor]:
+                         filter: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                         max_wrong: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
     """Plan.locate_batch over a ragged batch of stored chunks (slime_rs_locate_objects_batch; with
     a PlanSet and a planned batch every object takes its own plan,
     slime_rs_planset_locate_objects_batch): symbol = BE(word) ^ mapping[o], addressing and checks
     as verify_objects_batch.  Returns (counts, first) of shape (batch.nobj, k + rows + 1) exactly
     as Plan.locate_batch, or (batch.nobj, k + max_rows + 1) as PlanSet.locate_batch; filter is the
-    mismatches tensor of a preceding verify_objects_batch with the same plan or set, or None."""
+    mismatches tensor of a preceding verify_objects_batch with the same plan or set, or None.
+    max_wrong=2 takes the pair calls (slime_rs_locate_pairs_objects_batch /
+    slime_rs_planset_locate_pairs_objects_batch), as Plan.locate_batch does."""
+    pairs = _check_max_wrong(max_wrong)
     is_set = _check_objects_batch("locate_objects_batch", plan_or_set, src, cmp, batch, mapping)
     rows = plan_or_set.max_rows if is_set else plan_or_set.rows
     _check_locate_filter(filter, batch.nobj, rows, plan_or_set.device)
     counts, first = _verify_results(batch.nobj, plan_or_set.k + rows + 1, plan_or_set.device)
     if batch.nobj == 0:
         return counts, first  # no results: nothing to initialise, nothing to launch
-    call = lib.slime_rs_planset_locate_objects_batch if is_set else lib.slime_rs_locate_objects_batch
+    if pairs:
+        call = lib.slime_rs_planset_locate_pairs_objects_batch if is_set else lib.slime_rs_locate_pairs_objects_batch
+    else:
+        call = lib.slime_rs_planset_locate_objects_batch if is_set else lib.slime_rs_locate_objects_batch
     N.check(call(plan_or_set._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(cmp.data_ptr()),
                  ctypes.c_void_p(mapping.data_ptr()),
                  ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,

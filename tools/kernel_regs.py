@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register table of a HIP source's kernels for gfx950 (hipcc's
-kernel-resource-usage remarks): VGPRs, AGPRs, spills, LDS, waves per SIMD.
+kernel-resource-usage remarks): VGPRs, AGPRs, spills, scratch bytes a lane, waves per SIMD.
 
     python tools/kernel_regs.py slime_amd/csrc/rs_bytes_mfma.hip [--filter ILi5] [-D NAME=V ...]
 
@@ -27,6 +27,7 @@ def main():
     rows, cur = [], None
     for line in r.stderr.splitlines():
         m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]|"
+                      r"ScratchSize \[bytes/lane\]|"
                       r"Occupancy \[waves/SIMD\]): (\S+)", line)
         if not m:
             continue
@@ -42,7 +43,7 @@ def main():
         dem = subprocess.run(["c++filt", row["name"]], capture_output=True, text=True)
         name = dem.stdout.strip().split("(")[0]
         print(f"{row.get('VGPRs','?'):>4} v {row.get('AGPRs','?'):>3} a  spill v {row.get('VGPRs Spill','?'):>3} "
-              f"s {row.get('SGPRs Spill','?'):>3}  waves {row.get('Occupancy [waves/SIMD]','?'):>2}  {name}")
+              f"s {row.get('SGPRs Spill','?'):>3}  scratch {row.get('ScratchSize [bytes/lane]','?'):>3}  waves {row.get('Occupancy [waves/SIMD]','?'):>2}  {name}")
 
 
 if __name__ == "__main__":
