@@ -411,6 +411,10 @@ hipError_t launch_verify_bytes_ragged(const RaggedBytesVerifyLaunch& v, hipStrea
 //     slots k + rows_o .. k + max_rows - 1 keep their initial values.  An object whose plan has
 //     one row reports every mismatching column as unlocated.  Needs 2 <= max_rows and
 //     k + max_rows <= 63.
+//   pairs: the pair rule of locate_rule.hpp behind the one-shard rule -- a column with two wrong
+//     shards counts for both of its slots.  Needs 4 <= rows (a set: 4 <= max_rows; objects of fewer
+//     rows take the one-shard rule); everything else, results included, as without.  Uses
+//     rows x 256 words of dynamic LDS a block (at most 60 KiB), no scratch.
 struct RaggedLocateLaunch {
   const void* in;
   const void* cmp;
@@ -420,14 +424,9 @@ struct RaggedLocateLaunch {
   const uint64_t* filter;
   uint64_t* counts;
   uint64_t* first;
+  bool pairs;
 };
 hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t stream);
-// Pair locate (rs_locate_pairs_ragged.hip): the same launch with the pair rule of locate_rule.hpp
-// behind the one-shard rule -- a column with two wrong shards counts for both of its slots.
-// Needs 4 <= rows (a set: 4 <= max_rows; objects of fewer rows take the one-shard rule) and
-// k + rows <= 63; everything else, results included, as launch_locate_ragged.  Uses
-// rows x 256 words of dynamic LDS a block (at most 60 KiB), no scratch.
-hipError_t launch_locate_pairs_ragged(const RaggedLocateLaunch& v, hipStream_t stream);
 
 // --- ragged byte encode (rs_bytes_ragged_encode.hip) ------------------------------
 // The fused byte encode over a ragged batch: object o of sizes[o] bytes, its k

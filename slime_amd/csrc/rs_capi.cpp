@@ -762,7 +762,7 @@ int check_locate_batch(const char* what, bool set, bool pairs, uint32_t k, uint3
 }
 
 // Ragged locate (rs_locate_ragged.hip), symbols (bytes = false, no mapping) or stored chunk bytes;
-// pairs: the pair rule behind it (rs_locate_pairs_ragged.hip).
+// pairs: the pair rule behind it.
 template <class H>
 int locate_batch(const char* what, H* h, slime_rs_batch* batch, const void* src, const void* cmp, bool bytes,
                  const uint32_t* mapping, const uint64_t* filter, uint64_t* counts, uint64_t* first, void* stream,
@@ -774,11 +774,11 @@ int locate_batch(const char* what, H* h, slime_rs_batch* batch, const void* src,
   // The byte form is told from the symbol form by its mapping: required even when the batch is empty.
   if (bytes && !mapping) return fail(Status::InvalidArg, std::string(what) + ": null mapping");
   if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
-  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(h), mapping, filter, counts, first};
+  RaggedLocateLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(h), mapping, filter, counts, first, pairs};
   v.p.rows = result_rows(h);  // the result arrays' and the filter's row stride
   mark_launched(h);
   DeviceScope ds(h->device);
-  HIP_TRY(pairs ? launch_locate_pairs_ragged(v, (hipStream_t)stream) : launch_locate_ragged(v, (hipStream_t)stream));
+  HIP_TRY(launch_locate_ragged(v, (hipStream_t)stream));
   return 0;
 }
 
@@ -949,7 +949,7 @@ int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch
                       stream);
 }
 
-// ---- pair locate (rs_locate_pairs_ragged.hip) ---------------------------------------
+// ---- pair locate (rs_locate_ragged.hip, pairs) ---------------------------------------
 
 int slime_rs_plan_locate_pairs_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t* src,
                                      const uint32_t* cmp, const uint64_t* filter, uint64_t* counts, uint64_t* first,

@@ -7,6 +7,12 @@
 // slot), the tail items and the one-column-a-lane form.  rs_locate_ragged.hip's
 // header comment describes the scheme.
 //
+// PAIRS: the pair rule of locate_rule.hpp behind the one-shard rule.  A flagged
+// column goes through classify_pair_column, which leaves the column's syndromes
+// in the lane's slice of the block's LDS strip (`strip`, the bodies' last
+// argument; null without PAIRS) and may name two slots; tally_slots then runs
+// once per named slot, and a tail item issues its atomics for both.
+//
 // SET: `coeff` is the set's table (planset_table.hpp) and `rows` its max_rows,
 // in_idx / out_idx are null; when the walk enters an object its own plan -- k
 // input indices, coefficient rows, output indices, row count -- is read from
@@ -84,6 +90,62 @@ __device__ __forceinline__ uint32_t classify_column(const uint8_t* ib, const uin
   return c.slot(k, rows);
 }
 
+// The pair rule's classification of one column (locate_rule.hpp, pair_slots): classify_column's
+// pass, which also writes the column's syndromes into the lane's slice of the block's LDS strip --
+// `strip` is rows x kBlock words, s_i at strip[i * kBlock + threadIdx.x], so a wave's accesses to
+// one row fall into 64 consecutive words -- and keeps the d_i in a register mask.  A column the
+// one-shard rule leaves unlocated then goes through the pair enumeration, which reads the strip
+// and the plan's coefficient rows.  No per-row arrays in registers, nothing in scratch.
+template <bool BYTES>
+__device__ __forceinline__ Slots classify_pair_column(const uint8_t* ib, const uint8_t* cb,
+                                                      const uint32_t* __restrict__ coeff,
+                                                      const uint32_t* __restrict__ in_idx, uint64_t in_shard,
+                                                      const uint32_t* __restrict__ out_idx, uint64_t cmp_shard,
+                                                      uint32_t rows, uint32_t k, uint32_t m, uint64_t col,
+                                                      uint32_t* strip) {
+  const uint32_t cs = apply::wide_coeff_stride(k);
+  auto in_word = [&](uint32_t j) {
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(ib + (uint64_t)in_idx[j] * in_shard + (col << 2));
+    return BYTES ? be(v) ^ m : v;
+  };
+  uint32_t* const mine = strip + threadIdx.x;
+  Column c;
+  c.begin(k);
+  uint64_t dmask = 0;
+  for (uint32_t i = 0; i < rows; ++i) {
+    const uint32_t* const ci = coeff + (uint64_t)i * cs;
+    const uint32_t computed = apply::wide_dot(ci, k, in_word);
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(cb + (uint64_t)out_idx[i] * cmp_shard + (col << 2));
+    const uint32_t stored = BYTES ? be(w) ^ m : w;
+    c.row(i, computed, stored, coeff, ci);
+    dmask |= (uint64_t)(stored != computed) << i;
+    mine[i * kBlock] = sub(canon(stored), computed);
+  }
+  return pair_slots(
+      c.slot(k, rows), dmask, [&](uint32_t i) { return mine[i * kBlock]; },
+      [&](uint32_t i, uint32_t j) { return coeff[(uint64_t)i * cs + j]; }, k, rows);
+}
+
+// The slots column `col` names under the launch's rule, as either classification above takes its
+// arguments; max_rows: the set's, for set_slot.  Without PAIRS .b is kNoSlot.
+template <bool PAIRS, bool SET, bool BYTES>
+__device__ __forceinline__ Slots column_slots(const uint8_t* ib, const uint8_t* cb,
+                                              const uint32_t* __restrict__ coeff,
+                                              const uint32_t* __restrict__ in_idx, uint64_t in_shard,
+                                              const uint32_t* __restrict__ out_idx, uint64_t cmp_shard,
+                                              uint32_t rows, uint32_t k, uint32_t m, uint64_t col, uint32_t max_rows,
+                                              uint32_t* strip) {
+  if constexpr (PAIRS) {
+    Slots ps = classify_pair_column<BYTES>(ib, cb, coeff, in_idx, in_shard, out_idx, cmp_shard, rows, k, m, col, strip);
+    if constexpr (SET) ps = set_slots(ps, k, rows, max_rows);
+    return ps;
+  } else {
+    uint32_t slot = classify_column<BYTES>(ib, cb, coeff, in_idx, in_shard, out_idx, cmp_shard, rows, k, m, col);
+    if constexpr (SET) slot = set_slot(slot, k, rows, max_rows);
+    return Slots{slot, kNoSlot};
+  }
+}
+
 // Folds a wave's classified columns into its Tally, slot by slot: `slot` is this lane's column's
 // slot or kNoSlot, `col` its column; the lanes hold columns in ascending order, so the lowest lane
 // of a slot holds its lowest column.
@@ -156,9 +218,9 @@ __device__ __forceinline__ uint32_t flag_tile(uint4 (&x)[U][K], uint4 (&s)[R][U]
 
 // The tail items: one {object, column} per lane, classified and counted by the lane itself
 // (neighbouring lanes hold different objects: Tally's lane-per-slot scheme does not apply, and
-// with SET the lane reads its item's plan through its descriptor).
-template <bool SET, bool BYTES>
-__device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS) {
+// with SET the lane reads its item's plan through its descriptor), for both slots of a pair.
+template <bool PAIRS, bool SET, bool BYTES>
+__device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS, uint32_t* strip) {
   const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint64_t nthr = (uint64_t)gridDim.x * kBlock;
   const uint32_t nslots = k + rows + 1;
@@ -175,22 +237,30 @@ __device__ __forceinline__ void locate_tails(SLIME_RLOCATE_PARAMS) {
     }
     uint32_t m = 0;
     if constexpr (BYTES) m = mapping[it.obj];
-    uint32_t slot = classify_column<BYTES>(in + (d->src_off << 2), cmp + (d->dst_off << 2), pl.coeff, iidx,
-                                           d->src_shard << 2, pl.oidx, d->dst_shard << 2, pl.rows, k, m, it.col);
-    if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
-    if (slot != kNoSlot) {
-      atomicAdd(counts + (uint64_t)it.obj * nslots + slot, 1ull);
-      atomicMin(first + (uint64_t)it.obj * nslots + slot, (unsigned long long)it.col);
+    const Slots ps = column_slots<PAIRS, SET, BYTES>(in + (d->src_off << 2), cmp + (d->dst_off << 2), pl.coeff, iidx,
+                                                     d->src_shard << 2, pl.oidx, d->dst_shard << 2, pl.rows, k, m,
+                                                     it.col, rows, strip);
+    if (ps.a != kNoSlot) {
+      atomicAdd(counts + (uint64_t)it.obj * nslots + ps.a, 1ull);
+      atomicMin(first + (uint64_t)it.obj * nslots + ps.a, (unsigned long long)it.col);
+    }
+    if constexpr (PAIRS) {
+      if (ps.b != kNoSlot) {  // a pair: the column counts for both of its slots
+        atomicAdd(counts + (uint64_t)it.obj * nslots + ps.b, 1ull);
+        atomicMin(first + (uint64_t)it.obj * nslots + ps.b, (unsigned long long)it.col);
+      }
     }
   }
 }
 
 // Four columns a lane, k = K <= 16 over 4-byte aligned bases: a static walk over the unit list,
 // a tile in verify's steps of W vectors a lane, one step at a time.  With SET, R comes from the
-// set's max_rows; row_bases and flag_tile clip to the object's own rows.
-template <int K, int W, int R, int UB, int C, bool SET, bool BYTES>
-__device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS) {
+// set's max_rows; row_bases and flag_tile clip to the object's own rows.  PAIRS: R is 4 (pair
+// launches have rows >= 4).
+template <bool PAIRS, int K, int W, int R, int UB, int C, bool SET, bool BYTES>
+__device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS, uint32_t* strip) {
   static_assert(K > 0 && K <= 16 && W >= 1 && W <= UB && W <= 4, "compile-time k; a step is at most a tile");
+  static_assert(!PAIRS || R == 4, "the pair kernels carry four stored rows a step");
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t nslots = k + rows + 1;
@@ -215,10 +285,12 @@ __device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS) {
     if (w.fresh) {  // the first tile since the object changed
       skip = filtered_out(filter, w.obj, rows);
       if (!skip) {
-        // Two branches with the same three source-side statements: with SET the index line is read
-        // before them.  The statement order is what the kernels' machine code is compared by
-        // (tools/kernel_ids.py); a shared tail behind the read changes both families' kernels.
-        if constexpr (SET) {
+        // Two branches with the same three source-side statements: in the one-shard SET kernels the
+        // index line is read before them, in the pair SET kernels after them, as without SET.  The
+        // statement order is what the kernels' machine code is compared by (tools/kernel_ids.py):
+        // a shared tail behind the read changes both one-shard families' kernels, and the
+        // one-shard order changes the pair SET kernels.
+        if constexpr (SET && !PAIRS) {
           const PlanRef p = ragged::load_plan(coeff, descs, w.obj);
           pl = ragged::whole_plan(coeff, p);
           iidx = coeff + p.in_off;
@@ -232,8 +304,17 @@ __device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS) {
           if constexpr (BYTES) m = mapping[w.obj];  // wave-uniform
           ib = in + (w.d.src_off << 2);
           ishard = w.d.src_shard << 2;
+          if constexpr (SET) {
+            const PlanRef p = ragged::load_plan(coeff, descs, w.obj);
+            pl = ragged::whole_plan(coeff, p);
+            iidx = coeff + p.in_off;
+            const u32x16 idx = *reinterpret_cast<const u32x16*>(iidx);  // K <= 16: one line
 #pragma unroll
-          for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)in_idx[j] * ishard;
+            for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)idx[j] * ishard;
+          } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) sb[j] = ib + (uint64_t)in_idx[j] * ishard;
+          }
         }
         cb = cmp + (w.d.dst_off << 2);
         cshard = w.d.dst_shard << 2;
@@ -255,17 +336,28 @@ __device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS) {
             flag_tile<K, W, R, BYTES, uint32_t>(x, s, cb, pl.coeff, pl.oidx, cshard, pl.rows, m, tb, tend, lane);
         if (__ballot(bits != 0)) {
           // Rare path: word q & 3 of unit q >> 2, every lane that flagged it; for one q the lanes
-          // are in column order.
+          // are in column order, for a pair's first slots and for its second slots alike.
           for (uint32_t q = 0; q < 4u * W; ++q) {
             const bool hit = (bits >> q) & 1u;
             if (!__ballot(hit)) continue;
             const uint64_t col = ((uint64_t)(tb + 64 * (q >> 2) + lane) << 2) + (q & 3u);
-            uint32_t slot = kNoSlot;
-            if (hit) {
-              slot = classify_column<BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col);
-              if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
+            // The one-shard kernels keep their scalar slot: through column_slots' Slots, as in
+            // locate_tails and locate_columns, eight of them (BYTES, K <= 7) get other machine code.
+            if constexpr (PAIRS) {
+              Slots ps{kNoSlot, kNoSlot};
+              if (hit)
+                ps = column_slots<true, SET, BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col,
+                                                    rows, strip);
+              tally_slots(t, ps.a, col);
+              tally_slots(t, ps.b, col);
+            } else {
+              uint32_t slot = kNoSlot;
+              if (hit) {
+                slot = classify_column<BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col);
+                if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
+              }
+              tally_slots(t, slot, col);
             }
-            tally_slots(t, slot, col);
           }
         }
       }
@@ -273,14 +365,15 @@ __device__ __forceinline__ void locate_vectors(SLIME_RLOCATE_PARAMS) {
     w.advance();
   }
   t.flush();
-  locate_tails<SET, BYTES>(SLIME_RLOCATE_PASS);
+  locate_tails<PAIRS, SET, BYTES>(SLIME_RLOCATE_PASS, strip);
 }
 
 // One column a lane over the same unit list (static walk): generic k through wide_dot, any
 // alignment; with SET the unit's object's plan is read per unit.  tile_cols = 256 UB,
 // unit_tiles = C of the batch's geometry.
-template <bool SET, bool BYTES>
-__device__ __forceinline__ void locate_columns(SLIME_RLOCATE_PARAMS, uint32_t tile_cols, uint32_t unit_tiles) {
+template <bool PAIRS, bool SET, bool BYTES>
+__device__ __forceinline__ void locate_columns(SLIME_RLOCATE_PARAMS, uint32_t tile_cols, uint32_t unit_tiles,
+                                               uint32_t* strip) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t nwaves = gridDim.x * kWaves;
@@ -326,17 +419,17 @@ __device__ __forceinline__ void locate_columns(SLIME_RLOCATE_PARAMS, uint32_t ti
       }
       bad &= ok;
       if (__ballot(bad)) {
-        uint32_t slot = kNoSlot;
-        if (bad) {
-          slot = classify_column<BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col);
-          if constexpr (SET) slot = set_slot(slot, k, pl.rows, rows);
-        }
-        tally_slots(t, slot, col);
+        Slots ps{kNoSlot, kNoSlot};
+        if (bad)
+          ps = column_slots<PAIRS, SET, BYTES>(ib, cb, pl.coeff, iidx, ishard, pl.oidx, cshard, pl.rows, k, m, col,
+                                               rows, strip);
+        tally_slots(t, ps.a, col);
+        if constexpr (PAIRS) tally_slots(t, ps.b, col);
       }
     }
   }
   t.flush();
-  locate_tails<SET, BYTES>(SLIME_RLOCATE_PASS);
+  locate_tails<PAIRS, SET, BYTES>(SLIME_RLOCATE_PASS, strip);
 }
 
 }  // namespace locate

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register table of a HIP source's kernels for gfx950 (hipcc's
-kernel-resource-usage remarks): VGPRs, AGPRs, spills, scratch bytes a lane, waves per SIMD.
+kernel-resource-usage remarks): VGPRs, AGPRs, spills, scratch bytes a lane, static LDS bytes a
+block, waves per SIMD.
 
     python tools/kernel_regs.py slime_amd/csrc/rs_bytes_mfma.hip [--filter ILi5] [-D NAME=V ...]
 
@@ -43,7 +44,8 @@ def main():
         dem = subprocess.run(["c++filt", row["name"]], capture_output=True, text=True)
         name = dem.stdout.strip().split("(")[0]
         print(f"{row.get('VGPRs','?'):>4} v {row.get('AGPRs','?'):>3} a  spill v {row.get('VGPRs Spill','?'):>3} "
-              f"s {row.get('SGPRs Spill','?'):>3}  scratch {row.get('ScratchSize [bytes/lane]','?'):>3}  waves {row.get('Occupancy [waves/SIMD]','?'):>2}  {name}")
+              f"s {row.get('SGPRs Spill','?'):>3}  scratch {row.get('ScratchSize [bytes/lane]','?'):>3}  "
+              f"lds {row.get('LDS Size [bytes/block]','?'):>3}  waves {row.get('Occupancy [waves/SIMD]','?'):>2}  {name}")
 
 
 if __name__ == "__main__":
