@@ -251,10 +251,8 @@ __global__ __launch_bounds__(kBlock) void rs_decode_ragged_column_kernel(SLIME_B
       ii = coeff + p.in_off;
     }
     const uint32_t m = mapping[u.obj];
-    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
-    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)d.nvec << 2;
-    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
-    for (uint64_t b = b0 + lane; b < b1; b += 64)
+    const ragged::ColRange c = ragged::unit_columns(d.ntiles, u, tile_cols, unit_tiles, d.nvec);
+    for (uint64_t b = c.b0 + lane; b < c.b1; b += 64)
       decode_column<0>(in + (d.src_off << 2), out + (d.dst_off << 2), pl.coeff, ii, d.src_shard << 2, pl.oidx,
                        d.dst_shard << 2, pl.rows, k, m, b << 2);
   }

@@ -286,11 +286,9 @@ __global__ __launch_bounds__(kBlock) void rs_encode_ragged_column_kernel(SLIME_B
     const uint64_t L = descs[u.obj].ncols;
     const edge::Geom g = edge::geom(sizes[u.obj], L, k);
     const uint32_t m = pass ? mapping[u.obj] : 0u;
-    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
-    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)g.interior << 2;
-    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+    const ragged::ColRange c = ragged::unit_columns(d.ntiles, u, tile_cols, unit_tiles, g.interior);
     uint32_t bits = 0;
-    for (uint64_t b = b0 + lane; b < b1; b += 64)
+    for (uint64_t b = c.b0 + lane; b < c.b1; b += 64)
       bits |= encode_column<0>(in + (d.src_off << 2), out + (d.dst_off << 2), coeff, d.src_shard << 2, out_idx,
                                d.dst_shard << 2, rows, k, m, L, b, g);
     if (!pass) or_wave_flags(status, u.obj, bits, lane);

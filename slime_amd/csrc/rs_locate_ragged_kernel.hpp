@@ -392,9 +392,7 @@ __device__ __forceinline__ void locate_columns(SLIME_RLOCATE_PARAMS, uint32_t ti
     }
     uint32_t m = 0;
     if constexpr (BYTES) m = mapping[u.obj];
-    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
-    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)d.nvec << 2;
-    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+    const ragged::ColRange c = ragged::unit_columns(d.ntiles, u, tile_cols, unit_tiles, d.nvec);
     unsigned long long* const res = counts + (uint64_t)u.obj * nslots;
     if (res != t.mism) {
       t.flush();
@@ -403,9 +401,9 @@ __device__ __forceinline__ void locate_columns(SLIME_RLOCATE_PARAMS, uint32_t ti
     const uint8_t* const ib = in + (d.src_off << 2);
     const uint8_t* const cb = cmp + (d.dst_off << 2);
     const uint64_t ishard = d.src_shard << 2, cshard = d.dst_shard << 2;
-    for (uint64_t bw = b0; bw < b1; bw += 64) {
+    for (uint64_t bw = c.b0; bw < c.b1; bw += 64) {
       // bw is always inside the object; lanes past the last column re-read column bw and never count.
-      const bool ok = bw + lane < b1;
+      const bool ok = bw + lane < c.b1;
       const uint64_t col = ok ? bw + lane : bw;
       auto in_word = [&](uint32_t j) {
         const uint32_t v = *reinterpret_cast<const uint32_t*>(ib + (uint64_t)iidx[j] * ishard + (col << 2));

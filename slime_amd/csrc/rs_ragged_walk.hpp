@@ -1,9 +1,12 @@
 // A wave's walk over the unit list of a ragged batch (ragged_plan.hpp), and
 // the per-object loads that go with it: the object's descriptor and, in a
 // planned batch, the record of its plan in a plan set's table
-// (planset_table.hpp).  Shared by the apply kernels (rs_ragged.hip) and the
-// verify kernels (rs_verify_ragged.hip); rs_ragged.hip's header comment
-// describes the walk.
+// (planset_table.hpp); for the generic-k column kernels, which walk the list
+// without UnitWalk, a unit's column range (unit_columns).  Shared by every
+// ragged launch: apply (rs_ragged.hip), verify (rs_verify_ragged.hip), locate
+// (rs_locate_ragged.hip) and the byte forms (rs_bytes_ragged.hip,
+// rs_bytes_ragged_encode.hip); rs_ragged.hip's header comment describes the
+// walk.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +37,22 @@ __device__ __forceinline__ ObjRef load_desc(const Desc* __restrict__ descs, uint
   r.nvec = v[8];
   r.ntiles = v[9];
   return r;
+}
+
+// The columns [b0, b1) of unit u in an object of `ntiles` tiles, as the
+// generic-k column kernels read them: tile_cols columns a tile, up to
+// unit_tiles tiles from u.tile on, cut at vector `nvec` (the object's whole
+// vectors; byte encode passes its interior bound).  The unit goes by value:
+// by reference the apply's single-plan column kernel compiles to other bytes.
+struct ColRange {
+  uint64_t b0, b1;
+};
+__device__ __forceinline__ ColRange unit_columns(uint32_t ntiles, const Unit u, uint32_t tile_cols,
+                                                 uint32_t unit_tiles, uint32_t nvec) {
+  const uint32_t t1 = ntiles - u.tile < unit_tiles ? ntiles : u.tile + unit_tiles;
+  const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)nvec << 2;
+  const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+  return ColRange{b0, b1};
 }
 
 // A wave's walk over the unit list (device state, wave-uniform), with

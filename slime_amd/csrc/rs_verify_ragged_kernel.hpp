@@ -134,17 +134,15 @@ __device__ __forceinline__ void verify_ragged_columns(SLIME_RVERIFY_PARAMS, uint
     }
     uint32_t m = 0;
     if constexpr (BYTES) m = mapping[u.obj];
-    const uint32_t t1 = d.ntiles - u.tile < unit_tiles ? d.ntiles : u.tile + unit_tiles;
-    const uint64_t b0 = (uint64_t)u.tile * tile_cols, bmax = (uint64_t)d.nvec << 2;
-    const uint64_t b1 = (uint64_t)t1 * tile_cols < bmax ? (uint64_t)t1 * tile_cols : bmax;
+    const ragged::ColRange c = ragged::unit_columns(d.ntiles, u, tile_cols, unit_tiles, d.nvec);
     unsigned long long* const mi = mism + (uint64_t)u.obj * res_stride;
     if (mi != t.mism) {
       t.flush();
       t.begin(mi, first + (uint64_t)u.obj * res_stride);
     }
-    for (uint64_t bw = b0; bw < b1; bw += 64)
+    for (uint64_t bw = c.b0; bw < c.b1; bw += 64)
       check_columns<0, BYTES>(t, in + (d.src_off << 2), cmp + (d.dst_off << 2), pl.coeff, ii, d.src_shard << 2, pl.oidx,
-                              d.dst_shard << 2, pl.rows, k, m, bw, b1);
+                              d.dst_shard << 2, pl.rows, k, m, bw, c.b1);
   }
   t.flush();
   verify_tails<0, SET, BYTES>(SLIME_RVERIFY_PASS);
