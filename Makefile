@@ -8,7 +8,7 @@ SRC      := slime_amd/csrc
 OBJ      := build/obj
 LIB      := slime_amd/lib/libslime_rs.so
 
-OBJS := $(OBJ)/rs_apply.o $(OBJ)/rs_apply_k32.o $(OBJ)/rs_apply_mfma.o $(OBJ)/rs_verify.o $(OBJ)/rs_ragged.o $(OBJ)/rs_verify_ragged.o $(OBJ)/rs_locate_ragged.o $(OBJ)/rs_bytes.o $(OBJ)/rs_bytes_k32.o $(OBJ)/rs_bytes_mfma.o $(OBJ)/rs_bytes_ragged.o $(OBJ)/rs_bytes_ragged_encode.o $(OBJ)/gf_codec.o $(OBJ)/host_blit.o $(OBJ)/rs_matrix.o $(OBJ)/host_copy.o $(OBJ)/host_codec.o $(OBJ)/digest.o $(OBJ)/device_alloc.o $(OBJ)/host_pipeline.o $(OBJ)/go_api.o $(OBJ)/object_calls.o $(OBJ)/rs_capi.o
+OBJS := $(OBJ)/rs_apply.o $(OBJ)/rs_apply_k32.o $(OBJ)/rs_apply_mfma.o $(OBJ)/rs_verify.o $(OBJ)/rs_ragged.o $(OBJ)/rs_verify_ragged.o $(OBJ)/rs_locate_ragged.o $(OBJ)/rs_correct_ragged.o $(OBJ)/rs_bytes.o $(OBJ)/rs_bytes_k32.o $(OBJ)/rs_bytes_mfma.o $(OBJ)/rs_bytes_ragged.o $(OBJ)/rs_bytes_ragged_encode.o $(OBJ)/gf_codec.o $(OBJ)/host_blit.o $(OBJ)/rs_matrix.o $(OBJ)/host_copy.o $(OBJ)/host_codec.o $(OBJ)/digest.o $(OBJ)/device_alloc.o $(OBJ)/host_pipeline.o $(OBJ)/go_api.o $(OBJ)/object_calls.o $(OBJ)/rs_capi.o
 HDRS := $(wildcard $(SRC)/*.hpp) include/slime_rs.h
 
 CXXTEST  := tests/cpp/rs_host_test
@@ -27,9 +27,10 @@ EDGETEST := tests/cpp/encode_edge_test
 LOCATETEST := tests/cpp/locate_rule_test
 SETLOCATETEST := tests/cpp/planset_locate_rule_test
 PAIRLOCATETEST := tests/cpp/locate_pairs_rule_test
+CORRECTTEST := tests/cpp/correct_rule_test
 PROXYLOAD := tools/libproxy_load.so
 
-all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(LOCATETEST) $(SETLOCATETEST) $(PAIRLOCATETEST) $(PROXYLOAD)
+all: $(LIB) oracle $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(LOCATETEST) $(SETLOCATETEST) $(PAIRLOCATETEST) $(CORRECTTEST) $(PROXYLOAD)
 
 # Proxy-level load generator over the C-ABI (bench.py host_path.pooled): C++ threads, no GIL.
 $(PROXYLOAD): tools/proxy_load.cpp tools/crash_report.hpp include/slime_rs.h $(LIB)
@@ -56,6 +57,10 @@ $(LOCATETEST): tests/cpp/locate_rule_test.cpp $(SRC)/locate_rule.hpp $(SRC)/gfp.
 # The pair rule (locate_rule.hpp, pair_slots) against a brute-force statement by Gaussian elimination, CPU only.
 $(PAIRLOCATETEST): tests/cpp/locate_pairs_rule_test.cpp $(SRC)/locate_rule.hpp $(SRC)/gfp.hpp $(SRC)/gfp_host.hpp $(SRC)/rs_matrix.cpp $(SRC)/rs_matrix.hpp
 	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/locate_pairs_rule_test.cpp $(SRC)/rs_matrix.cpp
+
+# The correct rule (correct_rule.hpp) behind both locate rules: every planted slot and pair is restored exactly, CPU only.
+$(CORRECTTEST): tests/cpp/correct_rule_test.cpp $(SRC)/correct_rule.hpp $(SRC)/locate_rule.hpp $(SRC)/gfp.hpp $(SRC)/gfp_host.hpp $(SRC)/rs_matrix.cpp $(SRC)/rs_matrix.hpp
+	g++ -std=c++17 -O2 -Wall -Wextra -I$(SRC) -o $@ tests/cpp/correct_rule_test.cpp $(SRC)/rs_matrix.cpp
 
 # The plan-set addition to the locate rule (locate_rule.hpp, set_slot) against a brute-force statement, CPU only.
 $(SETLOCATETEST): tests/cpp/planset_locate_rule_test.cpp $(SRC)/locate_rule.hpp $(SRC)/gfp.hpp $(SRC)/gfp_host.hpp $(SRC)/rs_matrix.cpp $(SRC)/rs_matrix.hpp
@@ -123,7 +128,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(EDGETEST)_asan $(LOCATETEST) $(SETLOCATETEST) $(PAIRLOCATETEST)
+	rm -rf build $(LIB) $(PROXYLOAD) $(CXXTEST) $(CACHETEST) $(COPYTEST) $(POOLTEST) $(MFMATEST) $(FOLDTEST) $(DMATEST) $(REDOTEST) $(RAGGEDTEST) $(PLANSETTEST) $(STEPTEST) $(PROBETEST) $(EDGETEST) $(EDGETEST)_asan $(LOCATETEST) $(SETLOCATETEST) $(PAIRLOCATETEST) $(CORRECTTEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -593,8 +593,9 @@ int slime_rs_planset_locate_objects_batch(slime_rs_planset_t set, slime_rs_batch
  * capturable; the plan is marked launched.  SLIME_RS_ERR_INVALID_ARG, in this
  * order: the twin's handle and batch checks; rows < 4 (a set: max_rows < 4);
  * k + rows > 63; null result arrays; null buffers; for the byte forms a null
- * mapping.  Out of scope: three or more wrong shards per column, correcting in
- * place, matrix-core forms, k + rows > 63, device digests. */
+ * mapping.  Out of scope: three or more wrong shards per column, matrix-core
+ * forms, k + rows > 63, device digests.  Correcting in place: the correct calls
+ * below. */
 int slime_rs_plan_locate_pairs_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, const uint32_t *src,
                                      const uint32_t *cmp, const uint64_t *filter, uint64_t *counts, uint64_t *first,
                                      void *stream);
@@ -607,6 +608,68 @@ int slime_rs_planset_locate_pairs_batch(slime_rs_planset_t set, slime_rs_batch_t
 int slime_rs_planset_locate_pairs_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, const uint8_t *src,
                                                 const uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
                                                 uint64_t *counts, uint64_t *first, void *stream);
+
+/* ---- correct: fix the words locate names, in place ------------------------------
+ * The locate calls above that also REPAIR what they name: every column the rule
+ * names is rewritten where it is stored, so a following verify finds the column
+ * clean.  One flipped word costs a rewrite of that word, not a host round trip
+ * and a rewrite of its shard; verify -> correct is one capturable chain; and
+ * damage spread over more shards than the code has parity rows is repaired as
+ * long as each column has no more wrong shards than the rule handles (five
+ * shards of an 8/12 object wrong in five different columns: five erasures
+ * exceed four rows, column by column it is corrected).
+ * max_wrong: 1 is the one-shard rule (slime_rs_plan_locate_batch's), 2 the pair
+ * rule behind it (slime_rs_plan_locate_pairs_batch's, rows >= 4).  Arguments,
+ * addressing, the filter, the result arrays with their shape and
+ * initialisation, skipped objects (SLIME_RS_NO_PLAN, L == 0, cleared by the
+ * filter), the forms, the capture rules and the launched mark are each call's
+ * locate twin's; src and cmp are written.
+ * Per column, with s_i = stored_i - computed_i (mod p) and h_a the column of
+ * slot a as above:
+ *   clean or unlocated   nothing is written;
+ *   output row k + i     the stored word of row i becomes computed_i (two named
+ *                        rows: both);
+ *   input j alone        with r the first row of c[r][j] != 0 (row 0 for this
+ *                        library's plans), the word becomes
+ *                        x_j + s_r / c[r][j] (mod p);
+ *   a pair {a, b}        s = alpha*h_a + beta*h_b is solved from the non-zero
+ *                        minor the pair rule takes; an input a becomes
+ *                        x_a + alpha, an output row becomes the row over the
+ *                        corrected inputs (which is stored - beta).
+ * A named input whose coefficient column is all zero cannot be solved (only a
+ * slime_rs_plan_matrix plan can have one): nothing is written and the column is
+ * counted under `unlocated`.  For this library's MDS plans every coefficient is
+ * non-zero and counts / first equal the locate twin's exactly.
+ * The symbol forms write canonical residues: a wrong word whose original was
+ * the alias p + t comes back as t.  The byte forms write BE(sym ^ mapping[o]);
+ * stored symbols are below p by MapToGF's contract, so chunks come back bit for
+ * bit.  Only named words are written.
+ * Results: counts[o][slot] and first[o][slot] as locate's, now "columns
+ * corrected in this shard"; `unlocated` is what is left for erasure repair.
+ * The caller's contract, not checked (as slime_rs_plan_execute_batch's
+ * outputs): the shards a plan touches, and the objects of a batch, do not
+ * overlap in memory.  cmp may be src.
+ * Misattribution is locate's: more wrong shards in a column than the rule
+ * handles are unlocated, or "corrected" towards a wrong codeword, with
+ * probability about k / p per such column for max_wrong = 1 and about
+ * (k + rows)^2 / (2 p^(rows - 2)) for max_wrong = 2.
+ * Asynchronous, no scratch (max_wrong = 2: the twin's LDS strip), a static
+ * walk, no counter set, capturable.  SLIME_RS_ERR_INVALID_ARG, in this order:
+ * max_wrong neither 1 nor 2; then the locate twin's refusals in its order.
+ * Out of scope: three or more wrong shards per column, matrix-core forms,
+ * k + rows > 63, host-memory entry points, the Go shim. */
+int slime_rs_plan_correct_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, uint32_t *src, uint32_t *cmp,
+                                const uint64_t *filter, int max_wrong, uint64_t *counts, uint64_t *first,
+                                void *stream);
+int slime_rs_correct_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, uint8_t *src, uint8_t *cmp,
+                                   const uint32_t *mapping, const uint64_t *filter, int max_wrong, uint64_t *counts,
+                                   uint64_t *first, void *stream);
+int slime_rs_planset_correct_batch(slime_rs_planset_t set, slime_rs_batch_t batch, uint32_t *src, uint32_t *cmp,
+                                   const uint64_t *filter, int max_wrong, uint64_t *counts, uint64_t *first,
+                                   void *stream);
+int slime_rs_planset_correct_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, uint8_t *src,
+                                           uint8_t *cmp, const uint32_t *mapping, const uint64_t *filter,
+                                           int max_wrong, uint64_t *counts, uint64_t *first, void *stream);
 
 /* ---- ragged byte encode: ingest objects of different sizes in one launch -------
  * slime_rs_encode_objects over the spans of a batch, each object with its own

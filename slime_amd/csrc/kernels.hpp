@@ -428,6 +428,30 @@ struct RaggedLocateLaunch {
 };
 hipError_t launch_locate_ragged(const RaggedLocateLaunch& v, hipStream_t stream);
 
+// --- ragged correct (rs_correct_ragged.hip) ----------------------------------------
+// launch_locate_ragged that also rewrites, in place, every word the rule names
+// (correct_rule.hpp): an output row becomes the row computed over the corrected
+// inputs, an input x_j becomes x_j + s_r / c[r][j] (the pair rule: x_a + alpha).
+// Symbols are written as canonical residues, bytes as BE(sym ^ mapping[o]);
+// clean and unlocated columns are not written.  A named input whose coefficient
+// column is all zero cannot be solved: nothing is written and the column counts
+// as unlocated.  Everything else -- addressing, filter, results and their
+// initialisation, sets, pairs, forms, LDS, no scratch -- is RaggedLocateLaunch's.
+// in and cmp may be the same buffer; the shards a plan touches and the objects
+// of a batch must not overlap in memory (not checked).
+struct RaggedCorrectLaunch {
+  void* in;
+  void* cmp;
+  RaggedWork w;
+  RaggedPlan p;             // one plan, or a set's table
+  const uint32_t* mapping;  // bytes: nobj mapping values (device); symbols: nullptr
+  const uint64_t* filter;
+  uint64_t* counts;
+  uint64_t* first;
+  bool pairs;
+};
+hipError_t launch_correct_ragged(const RaggedCorrectLaunch& v, hipStream_t stream);
+
 // --- ragged byte encode (rs_bytes_ragged_encode.hip) ------------------------------
 // The fused byte encode over a ragged batch: object o of sizes[o] bytes, its k
 // data chunks read (and their tails rewritten) through the descriptor's src

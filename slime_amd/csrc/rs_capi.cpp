@@ -782,6 +782,30 @@ int locate_batch(const char* what, H* h, slime_rs_batch* batch, const void* src,
   return 0;
 }
 
+// Ragged correct (rs_correct_ragged.hip): locate_batch's checks behind one of its own, then the
+// launch that also rewrites what the rule names.  max_wrong: 1 the one-shard rule, 2 the pair rule.
+template <class H>
+int correct_batch(const char* what, H* h, slime_rs_batch* batch, void* src, void* cmp, bool bytes,
+                  const uint32_t* mapping, const uint64_t* filter, int max_wrong, uint64_t* counts, uint64_t* first,
+                  void* stream) {
+  if (max_wrong != 1 && max_wrong != 2)
+    return fail(Status::InvalidArg, std::string(what) + ": max_wrong = " + std::to_string(max_wrong) +
+                                        " is neither 1 (one wrong shard per column) nor 2 (a pair)");
+  const bool pairs = max_wrong == 2;
+  if (int rc = check_batch(what, h, batch)) return rc;
+  if (int rc = check_locate_batch(what, std::is_same<H, slime_rs_planset>::value, pairs, h->k, result_rows(h), src,
+                                  cmp, counts, first))
+    return rc;
+  if (bytes && !mapping) return fail(Status::InvalidArg, std::string(what) + ": null mapping");
+  if (batch->counts.nobj == 0) return 0;  // no results to initialise, nothing to launch
+  RaggedCorrectLaunch v{src, cmp, batch_work(batch, src, cmp), plan_side(h), mapping, filter, counts, first, pairs};
+  v.p.rows = result_rows(h);  // the result arrays' and the filter's row stride
+  mark_launched(h);
+  DeviceScope ds(h->device);
+  HIP_TRY(launch_correct_ragged(v, (hipStream_t)stream));
+  return 0;
+}
+
 }  // namespace
 extern "C" {
 
@@ -977,6 +1001,36 @@ int slime_rs_planset_locate_pairs_objects_batch(slime_rs_planset_t set, slime_rs
                                                 uint64_t* counts, uint64_t* first, void* stream) {
   return locate_batch("planset_locate_pairs_objects_batch", set, batch, src, cmp, true, mapping, filter, counts,
                       first, stream, true);
+}
+
+// ---- ragged correct (rs_correct_ragged.hip) ------------------------------------------
+
+int slime_rs_plan_correct_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, uint32_t* src, uint32_t* cmp,
+                                const uint64_t* filter, int max_wrong, uint64_t* counts, uint64_t* first,
+                                void* stream) {
+  return correct_batch("plan_correct_batch", plan, batch, src, cmp, false, nullptr, filter, max_wrong, counts, first,
+                       stream);
+}
+
+int slime_rs_correct_objects_batch(slime_rs_plan_t plan, slime_rs_batch_t batch, uint8_t* src, uint8_t* cmp,
+                                   const uint32_t* mapping, const uint64_t* filter, int max_wrong, uint64_t* counts,
+                                   uint64_t* first, void* stream) {
+  return correct_batch("correct_objects_batch", plan, batch, src, cmp, true, mapping, filter, max_wrong, counts,
+                       first, stream);
+}
+
+int slime_rs_planset_correct_batch(slime_rs_planset_t set, slime_rs_batch_t batch, uint32_t* src, uint32_t* cmp,
+                                   const uint64_t* filter, int max_wrong, uint64_t* counts, uint64_t* first,
+                                   void* stream) {
+  return correct_batch("planset_correct_batch", set, batch, src, cmp, false, nullptr, filter, max_wrong, counts,
+                       first, stream);
+}
+
+int slime_rs_planset_correct_objects_batch(slime_rs_planset_t set, slime_rs_batch_t batch, uint8_t* src,
+                                           uint8_t* cmp, const uint32_t* mapping, const uint64_t* filter,
+                                           int max_wrong, uint64_t* counts, uint64_t* first, void* stream) {
+  return correct_batch("planset_correct_objects_batch", set, batch, src, cmp, true, mapping, filter, max_wrong,
+                       counts, first, stream);
 }
 
 int slime_rs_plan_set_outputs(slime_rs_plan_t plan, const int* out_shards) {

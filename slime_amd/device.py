@@ -319,6 +319,31 @@ class Plan:
                      _stream_handle(self.device, stream)))
         return counts, first
 
+    def correct_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: "Batch", filter: Optional[torch.Tensor] = None,
+                      stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+                      cmp_offset: int = 0, max_wrong: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+        """locate_batch that also fixes what it names, in place (slime_rs_plan_correct_batch): every
+        column the rule names is rewritten in src / cmp -- an output row to the row over the
+        corrected inputs, an input to the value the syndromes solve for -- as canonical residues, so
+        a following verify_batch finds it clean.  Arguments, checks and the returned (counts, first)
+        are locate_batch's; counts[o, s] now reads "columns of object o corrected in slot s", and
+        the last column (`unlocated`) is what is left for erasure repair.  max_wrong=1 handles one
+        wrong shard per column, max_wrong=2 (rows >= 4) two.  The shards the plan touches and the
+        objects of the batch must not overlap in memory (not checked); cmp may be src."""
+        _check_max_wrong(max_wrong)
+        _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
+        _check_locate_filter(filter, batch.nobj, self.rows, self.device)
+        counts, first = _verify_results(batch.nobj, self.k + self.rows + 1, self.device)
+        if batch.nobj == 0:
+            return counts, first  # no results: nothing to initialise, nothing to launch
+        N.check(lib.slime_rs_plan_correct_batch(
+            self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+            ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+            ctypes.c_void_p(filter.data_ptr()) if filter is not None else None, max_wrong,
+            ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+            _stream_handle(self.device, stream)))
+        return counts, first
+
     def locate_slots(self) -> list[int]:
         """The shard index of each of the k + rows slots of locate_batch's results: the plan's
         input shards, then its output shards (as set_outputs left them)."""
@@ -576,6 +601,28 @@ class PlanSet:
                      ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
                      ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
                      _stream_handle(self.device, stream)))
+        return counts, first
+
+    def correct_batch(self, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, filter: Optional[torch.Tensor] = None,
+                      stream: Optional[torch.cuda.Stream] = None, src_offset: int = 0,
+                      cmp_offset: int = 0, max_wrong: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+        """Plan.correct_batch with every object corrected by its own plan of the set
+        (slime_rs_planset_correct_batch).  Arguments, checks and results are locate_batch's.  With
+        max_wrong=2 an object whose own plan has four rows or more takes the pair rule, one of two
+        or three rows the one-shard rule; an object of one row has every mismatching column
+        unlocated and nothing of it is written."""
+        _check_max_wrong(max_wrong)
+        _check_symbols_batch(self, src, cmp, batch, src_offset, cmp_offset)
+        _check_locate_filter(filter, batch.nobj, self.max_rows, self.device)
+        counts, first = _verify_results(batch.nobj, self.k + self.max_rows + 1, self.device)
+        if batch.nobj == 0:
+            return counts, first  # no results: nothing to initialise, nothing to launch
+        N.check(lib.slime_rs_planset_correct_batch(
+            self._h, batch._h, ctypes.c_void_p(src.data_ptr() + 4 * src_offset),
+            ctypes.c_void_p(cmp.data_ptr() + 4 * cmp_offset),
+            ctypes.c_void_p(filter.data_ptr()) if filter is not None else None, max_wrong,
+            ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+            _stream_handle(self.device, stream)))
         return counts, first
 
     def locate_slots(self, i: int) -> list:
@@ -911,6 +958,29 @@ def locate_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batc
     N.check(call(plan_or_set._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(cmp.data_ptr()),
                  ctypes.c_void_p(mapping.data_ptr()),
                  ctypes.c_void_p(filter.data_ptr()) if filter is not None else None,
+                 ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                 _stream_handle(plan_or_set.device, stream)))
+    return counts, first
+
+
+def correct_objects_batch(plan_or_set, src: torch.Tensor, cmp: torch.Tensor, batch: Batch, mapping: torch.Tensor,
+                          filter: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                          max_wrong: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+    """Plan.correct_batch over a ragged batch of stored chunks (slime_rs_correct_objects_batch /
+    slime_rs_planset_correct_objects_batch): locate_objects_batch that also rewrites every word it
+    names as BE(sym ^ mapping[o]), so damaged chunks come back bit for bit.  Arguments, checks and
+    results are locate_objects_batch's; src and cmp are written, and cmp may be src."""
+    _check_max_wrong(max_wrong)
+    is_set = _check_objects_batch("correct_objects_batch", plan_or_set, src, cmp, batch, mapping)
+    rows = plan_or_set.max_rows if is_set else plan_or_set.rows
+    _check_locate_filter(filter, batch.nobj, rows, plan_or_set.device)
+    counts, first = _verify_results(batch.nobj, plan_or_set.k + rows + 1, plan_or_set.device)
+    if batch.nobj == 0:
+        return counts, first  # no results: nothing to initialise, nothing to launch
+    call = lib.slime_rs_planset_correct_objects_batch if is_set else lib.slime_rs_correct_objects_batch
+    N.check(call(plan_or_set._h, batch._h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(cmp.data_ptr()),
+                 ctypes.c_void_p(mapping.data_ptr()),
+                 ctypes.c_void_p(filter.data_ptr()) if filter is not None else None, max_wrong,
                  ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(first.data_ptr()),
                  _stream_handle(plan_or_set.device, stream)))
     return counts, first
